@@ -107,6 +107,56 @@ def cpu_baseline(cfg, taxdir, sample):
                           half, se, fo, tc, threads, co)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_WINDOWS, DUMP_WINDOW, DUMP_SEED = 16, 1024, 2718
+HIT_COLUMNS = ("subject", "qstart", "qend", "sstart", "send", "score", "mismatch", "gapopen")
+
+
+def dump_outputs(out_dir, hits, recs, first):
+    """--dump-outputs: what the last timed step computed, so that two builds can be compared output for output.  The sample
+    is fixed by the batch size alone: DUMP_WINDOWS windows of DUMP_WINDOW consecutive reads at seeded places (the whole batch
+    when it is smaller).  Per sampled read: its number in the read stream, how many -outfmt 6 rows it has, its consensus
+    record (the "#Matches found" count; the winning row as its rank among the read's rows followed by that row's
+    HIT_COLUMNS, -1 throughout when the read has none).  Then the rows themselves (read number + HIT_COLUMNS) in table
+    order, cut at a whole row once the files would pass DUMP_LIMIT_BYTES.  float64 throughout: every value is an integer."""
+    import numpy as np
+    n = len(recs)
+    if n < DUMP_WINDOWS * DUMP_WINDOW:
+        starts, width = [0], n
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        starts = sorted(int(w) * DUMP_WINDOW for w in rng.choice(n // DUMP_WINDOW, DUMP_WINDOWS, replace=False))
+        width = DUMP_WINDOW
+    batch_off = hits.read_offsets(n)
+    read_index, read_rows, matches, winner, rows = [], [], [], [], []
+    for s in starts:
+        with hits.slice(s, width) as w:  # slots, read numbers and offsets of the window from 0
+            slots, off, shown = w.rows(width)
+            cnt = w.read_counts(width)
+        tab = np.stack([slots[c].astype(np.float64) for c in HIT_COLUMNS], axis=1)
+        rec = recs[s:s + width]
+        win = np.full((width, 1 + len(HIT_COLUMNS)), -1.0)
+        has = rec["hit"] >= 0
+        slot = rec["hit"][has].astype(np.int64) - batch_off[s]
+        win[has, 0] = slot - off[:-1][has]
+        win[has, 1:] = tab[slot]
+        read_index.append(first + s + np.arange(width, dtype=np.float64))
+        read_rows.append(cnt.astype(np.float64))
+        matches.append(rec["matches"].astype(np.float64))
+        winner.append(win)
+        rows.append(np.column_stack([first + s + slots["read"].astype(np.float64), tab])[shown])
+    out = {"read_index": np.concatenate(read_index), "read_rows": np.concatenate(read_rows),
+           "consensus_matches": np.concatenate(matches), "consensus_winner": np.concatenate(winner)}
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values()) - 128 * (len(out) + 1)  # (.npy headers)
+    rows = np.concatenate(rows)
+    out["hit_rows"] = rows[:max(0, room) // (rows.itemsize * rows.shape[1])]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print("bench.py: wrote %s (%d reads, %d of their %d rows)" % (", ".join(k + ".npy" for k in out), len(out["read_index"]),
+                                                                 len(out["hit_rows"]), len(rows)), file=sys.stderr, flush=True)
+
+
 def inclusive(pg, _capi, cfg, db, tmp, first, n):
     """File to file on a bounded sample: a FASTA file and an RDP file in (page cache), the Consensus text out -- the rate a
     user of the command lines sees.  The resident rate (`value`) leaves out everything measured here except the kernels."""
@@ -150,10 +200,16 @@ def main():
     ap.add_argument("--dry-ranks", action="store_true",
                     help="set-up only: build / broadcast / import the database, print one line per rank (device, free HBM, broadcast and "
                          "rebuild seconds, database checksums) and fail with the rank's number if a rank's copy differs; no timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's batch) as DIR/<name>.npy: the "
+                         "consensus records and -outfmt 6 rows of a fixed, seeded sample of its reads, float64, at most 64 MB; that "
+                         "step also hands its records and hit table to the host, as a caller of the path receives them")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: this process has not touched the GPU (nor imported torch), so it
         # may start the ranks itself -- as a CHILD process whose output and exit status it relays (the `mpirun -np N` of
@@ -291,9 +347,13 @@ def main():
             rdp = pg.Rdp.from_synth(cfg, first, B, db)
             batches.append((reads, rdp))
 
-        def step(i):
+        kept = {}
+
+        def step(i, keep=False):
             reads, rdp = batches[i % len(batches)]
-            _capi.classify_consensus(db, reads, rdp, want_records=False, want_hits=False)
+            hits, recs = _capi.classify_consensus(db, reads, rdp, want_records=keep, want_hits=keep)
+            if keep:
+                kept.update(hits=hits, recs=recs, first=sharding_first(i % len(batches), rank, world, B))
             return _capi.stage_times()
 
         def fence():
@@ -310,8 +370,9 @@ def main():
         fence()
         t0 = time.perf_counter()
         kernel_ms, alg_bytes, gap_ms, gap_bytes, stages = 0.0, 0, 0.0, 0, []
+        last_step = args.warmup + args.steps - 1
         for i in range(args.warmup, args.warmup + args.steps):
-            st = step(i)
+            st = step(i, keep=args.dump_outputs is not None and i == last_step)
             kernel_ms += st.seed_extend_ms
             alg_bytes += algorithmic_bytes(B, st, cfg.read_len)
             gap_ms += st.gapped_ms
@@ -323,6 +384,10 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if kept:
+            if rank == 0:
+                dump_outputs(args.dump_outputs, kept["hits"], kept["recs"], kept["first"])
+            kept.clear()  # (the hit table of a full batch is several GB of HBM)
         # the same K steps with the DUST bits of the batch import reused (the search then skips its first stage): a side line
         fence()
         db.set_dust_each_search(False)
