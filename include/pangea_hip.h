@@ -390,6 +390,8 @@ typedef struct {
 	int64_t gapped_wide; /* HSPs the first tier of the gapped stage listed for the later ones */
 	float dust_ms;       /* S3d recomputed inside the search (pgx_db_set_dust_each_search), else 0; part of total_ms */
 	int32_t attempts;    /* 1, or more when a table or list of the step was too small and the step was repeated with larger ones */
+	int32_t grown;       /* which buffers made the step repeat, OR-ed over its attempts: 1 the seed table, 2 the overflow table,
+	                      * 4 a list of the gapped stage's tiers, 8 the hit table; 0 when it ran once */
 } pgx_stage_times;
 int pgx_last_stage_times(pgx_stage_times *out);
 

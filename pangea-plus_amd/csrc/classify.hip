@@ -2227,18 +2227,22 @@ int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out
 		if (h_cnt[0] > cap) {
 			cap = h_cnt[0] + h_cnt[0] / 8;
 			again = true;
+			tm.grown |= 1;
 		}
 		if (H_ovf > ovf_cap) {
 			ovf_cap = H_ovf + H_ovf / 8;
 			again = true;
+			tm.grown |= 2;
 		}
 		if (dv.gapped && gap_listed > gap_cap) {
 			PGX_TRY(ws.gapped.big_list.ensure(gap_listed + gap_listed / 8));
 			again = true;
+			tm.grown |= 4;
 		}
 		if (!again && H > table_cap) { // (H is only exact once the seed tables held everything)
 			table_cap = H + H / 16;
 			again = true;
+			tm.grown |= 8;
 		}
 		tm.attempts = attempt + 1;
 		if (!again)

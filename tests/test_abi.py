@@ -102,3 +102,17 @@ def test_tax_class_cli_bytes_and_status(pg, taxdir, gold):
     for case in golden["cli"][::5]:
         p = subprocess.run([exe] + case["args"], cwd=taxdir, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         assert p.stdout.decode("latin-1") == case["stdout"] and p.returncode == case["rc"], case["args"]
+
+
+def test_stage_times_struct_follows_the_header():
+    """pgx_last_stage_times copies the whole C struct into the ctypes buffer: the Python mirror must name the same fields in
+    the same order, or the copy runs past it.  The last two say whether a search step was repeated and which buffer made it."""
+    from pangea_plus_amd import _capi
+    text = open(os.path.join(ROOT, "include", "pangea_hip.h")).read()
+    body = re.search(r"typedef struct \{([^}]*)\} pgx_stage_times;", text).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.split()[1:]]
+    names = [n for part in names for n in part.split(",") if n]
+    fields = [f[0] for f in _capi.StageTimes._fields_]
+    assert fields == names
+    assert fields[-2:] == ["attempts", "grown"]
