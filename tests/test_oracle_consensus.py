@@ -69,3 +69,84 @@ def test_three_way_vote_rules(oracle_bin, tmp_path):
                    "c\t[0]Bacteria;[1]Firmicutes;\t2\t22",               # no BLAST row: S = R
                    "d\t[0]Bacteria;[1]Firmicutes;\t2\t22",               # B = S on the domain, S = R on the phylum
                    "e\t\t0\t"]
+
+
+# ---------------------------------------------------------------- the plain restatement (tests/consensus_rule.py)
+import collections
+
+import pytest
+
+import consensus_inputs
+import consensus_rule
+
+VARIANTS = {"rm_numeric": consensus_rule.Variant(rm_numeric=True),
+            "count_numeric": consensus_rule.Variant(count_numeric=True),
+            "sim_numeric": consensus_rule.Variant(sim_numeric=True),
+            "last_tie": consensus_rule.Variant(last_tie=True),
+            "keep_maxcount": consensus_rule.Variant(keep_maxcount=True),
+            "no_undef_rank": consensus_rule.Variant(no_undef_rank=True)}
+
+
+def test_rule_restates_the_reference_goldens(gold):
+    cases = sorted(glob.glob(os.path.join(gold, "consensus", "*.blast.tsv")))
+    assert len(cases) >= 13
+    for b in cases:
+        name = b[:-len(".blast.tsv")]
+        out, log, recs = consensus_rule.consensus(open(b, "rb").read(), open(name + ".rdp.tsv", "rb").read())
+        assert out == open(name + ".out.txt", "rb").read(), name
+        assert log == open(name + ".log.txt", "rb").read(), name
+        assert len(recs) == out.count(b"#Matches found: ")
+
+
+def test_rule_flags_the_reference_hang(tmp_path):
+    with pytest.raises(consensus_rule.ReferenceHang):
+        consensus_rule.consensus(b"q1\t[0]Bacteria;\t99.0\t1\n",
+                                 b"q1\t\t\t\t\tBacteria\tdomain\t1.0\nq2\t\t\t\t\tBacteria\tdomain\t1.0\n")
+
+
+@pytest.fixture(scope="module")
+def paths(tmp_path_factory, oracle_bin):
+    return consensus_inputs.build(tmp_path_factory.mktemp("paths"), oracle_bin)
+
+
+@pytest.mark.parametrize("tax", ["T1", "T2", "T3"])
+def test_rule_equals_the_oracle_chain(paths, tax):
+    out, log, recs, _, _ = consensus_inputs.labelled(paths, tax)
+    assert out == open(paths["cons_" + tax], "rb").read()
+    assert len(recs) > 500
+    assert log.count(b"not found: ") > 0        # the reads without a line were skipped row by row
+
+
+def test_inputs_reach_every_form(paths):
+    """Every (hit group x selection form) cell holds at least 10 reads, some of whose winners are not the first row;
+    every record width and compare grid is reached by one taxonomy at least."""
+    cells, later = collections.Counter(), collections.Counter()
+    grids, widths = collections.Counter(), set()
+    for tax in ("T1", "T2", "T3"):
+        _, _, recs, db_pairs, nr_max = consensus_inputs.labelled(paths, tax)
+        widths.add(32 if db_pairs <= 7 else 64)
+        for r in recs:
+            cells[r.group, r.form] += 1
+            later[r.group, r.form] += r.row > 0
+            if r.group != "big":
+                grids[tax, r.grid] += 1
+    table = "\n".join("%-5s %-7s %4d reads, %4d won by a later row" % (g, f, cells[g, f], later[g, f])
+                      for g in ("le32", "le64", "big") for f in ("closed", "chain", "walk", "zero"))
+    print("\n" + table + "\n" + "\n".join("%s %-7s %4d reads" % (t, g, n) for (t, g), n in sorted(grids.items())))
+    for g in ("le32", "le64", "big"):
+        for f in ("closed", "chain", "walk", "zero"):
+            assert cells[g, f] >= 10 and later[g, f] > 0, (g, f, table)
+    assert widths == {32, 64}
+    assert grids["T1", "7x6"] > 0 and grids["T2", "15x8"] > 0      # the two grids over the same lineages
+    assert grids["T2", "general"] > 0 and grids["T3", "escape"] > 0 and grids["T3", "15x8"] > 0
+
+
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+def test_inputs_tell_wrong_restatements_apart(paths, variant):
+    changed = 0
+    for tax in ("T1", "T2", "T3"):
+        _, _, want, _, _ = consensus_inputs.labelled(paths, tax)
+        _, _, got, _, _ = consensus_inputs.labelled(paths, tax, VARIANTS[variant])
+        assert len(got) == len(want)
+        changed += sum((a.row, a.matches) != (b.row, b.matches) for a, b in zip(want, got))
+    assert changed >= 5, variant
