@@ -136,6 +136,13 @@ typedef struct {
 } pgx_soap_opts;
 int pgx_soap_index(const char *fasta_path); /* writes <fasta>.index.pgxdb */
 int pgx_soap_run(const pgx_soap_opts *opts);
+/* the same single-end run with a seed (soap.man:59-72: `-l seed_len`, the read's first bases; `-v max_total_mis`, the
+ * mismatches allowed outside it), as the ELF runs when -l or -v is given: a read with no whole-read placement is placed
+ * by its seed (<= 2 mismatches, -M picks by them) with at most max_total_mis (capped at 20) mismatches elsewhere, reads of
+ * any length; -l under 27 or not shorter than the read places it whole.  Rules: DESIGN section 10.  With reads_b_path
+ * set: PGX_E_LIMIT (paired-end seed rules were not observed).  A separate entry, so callers of pgx_soap_run keep the
+ * struct's layout. */
+int pgx_soap_run_seeded(const pgx_soap_opts *opts, int seed_len, int max_total_mis);
 
 /* ------------------------------------------------------------------------------------------
  * Taxonomy database  —  Tax_class/ncbitc.c.  Same file names in `dir` as the reference

@@ -90,7 +90,7 @@ SYMBOLS = [
     "pgx_last_error", "pgx_version", "pgx_init", "pgx_device_count", "pgx_current_device", "pgx_db_build", "pgx_db_open",
     "pgx_db_from_fasta", "pgx_db_close", "pgx_db_num_seqs", "pgx_db_num_bases", "pgx_db_seq_id",
     "pgx_db_device_arrays", "pgx_db_get_shape", "pgx_db_alloc_like", "pgx_db_finish_import", "pgx_db_checksum", "pgx_blastn_run", "pgx_db_set_ungapped", "pgx_db_set_dust", "pgx_db_set_dust_each_search",
-    "pgx_soap_index", "pgx_soap_run", "pgx_tax_create", "pgx_tax_open", "pgx_tax_close", "pgx_tax_gi2taxid",
+    "pgx_soap_index", "pgx_soap_run", "pgx_soap_run_seeded", "pgx_tax_create", "pgx_tax_open", "pgx_tax_close", "pgx_tax_gi2taxid",
     "pgx_tax_node", "pgx_tax_names", "pgx_tax_format_node", "pgx_tax_format_name", "pgx_tax_cli", "pgx_free",
     "pgx_tax_lineage_batch", "pgx_taxcollect_file", "pgx_consensus_file", "pgx_synth_default", "pgx_db_from_synth",
     "pgx_synth_write_taxdump", "pgx_reads_from_fasta", "pgx_reads_from_fasta_text", "pgx_reads_from_synth", "pgx_reads_write_fasta", "pgx_reads_redo_dust", "pgx_rdp_write_file", "pgx_reads_close", "pgx_reads_count",
@@ -524,11 +524,15 @@ def soap_index(fasta):
     _check(lib().pgx_soap_index(_b(fasta)))
 
 
-def soap(a, D, o, u=None, M=4, r=1, n=5, t=False, b=None, unpaired=None, m=400, x=600):
+def soap(a, D, o, u=None, M=4, r=1, n=5, t=False, b=None, unpaired=None, m=400, x=600, *, l=None, v=None):
     """`soap -a reads -D ref.index -o out [-u unmapped] -M 4 -r 1 -n 5` (reference README.md:134); paired-end with
-    `b` (-b), `unpaired` (-2), `m` / `x` (-m / -x), soap.man:29-50."""
+    `b` (-b), `unpaired` (-2), `m` / `x` (-m / -x), soap.man:29-50; single-end with a seed with `l` (-l, default 256) and
+    `v` (-v, default 5), soap.man:59-72 -- the seeded run only when one of them is given."""
     opts = _SoapOpts(_b(a), _b(D), _b(o), _b(u), M, r, n, int(bool(t)), _b(b), _b(unpaired), m, x)
-    _check(lib().pgx_soap_run(C.byref(opts)))
+    if l is None and v is None:
+        _check(lib().pgx_soap_run(C.byref(opts)))
+    else:
+        _check(lib().pgx_soap_run_seeded(C.byref(opts), 256 if l is None else int(l), 5 if v is None else int(v)))
 
 
 def tax_class(args, cwd="."):

@@ -13,6 +13,10 @@
 //   pass 0 finds the minimum mismatch count and how many placements reach it; the wavefront then reserves the read's rows
 //   in the hit list with ONE atomic (a read's rows are contiguous: first_hit[r] .. + n_best[r]) and pass 1 writes them.
 //   mode 5 (paired-end) keeps every placement with <= 2 mismatches.
+//   seed mode (k_soap_search<true>, `-l L -v V`, soap.man:59-72, single-end): a read with no whole-read placement gets a
+//   second phase over its seed, the read's first L bases (on '-' the reverse complement's last L): <= 2 mismatches in
+//   the seed, <= V outside it; the passes count and rank by the seed's mismatches; the total goes into bits 24-31 of
+//   strand_nmis, kSeededHit into bit 16.  Rules observed on the ELF: DESIGN section 10, tests/golden/soap_seed/.
 // k_soap_pair  one wavefront per read pair: counts the valid pairs of placements at mismatch levels 0, 1, 2.
 //   Seeds: three disjoint exact 16-mers per strand (pigeonhole for <= 2 mismatches) when the read
 //   has >= 48 bases, else the 1 129 variants of the first 16-mer with <= 2 substitutions.  Seeds hit
@@ -28,8 +32,9 @@ namespace pgx {
 struct SoapHit {
 	uint32_t read, subject, pos; // pos: 0-based leftmost position in the subject
 	int32_t mis0, mis1;          // reference-oriented mismatch offsets, ascending (-1 = none)
-	uint32_t strand_nmis;        // strand << 8 | nmis
+	uint32_t strand_nmis;        // strand << 8 | nmis; seed mode: | kSeededHit, | total mismatches << 24
 };
+constexpr uint32_t kSeededHit = 1u << 16; // placed by its seed: nmis, mis0 and mis1 describe the seed only
 
 struct SoapView {
 	const uint64_t *words;
@@ -40,6 +45,8 @@ struct SoapView {
 };
 
 constexpr int kVariants = 1 + 16 * 3 + 120 * 9; // 16-mer with <= 2 substitutions
+constexpr int kSoapMinSeed = 27;                  // -l under this: the ELF places reads whole (as without -l)
+constexpr int kSoapMaxRest = 20;                  // -v above this: the ELF's rows of -v 20
 
 // v-th variant of a 16-mer (v = 0 is the k-mer itself)
 __device__ __forceinline__ uint32_t kmer_variant(uint32_t kmer, int v)
@@ -91,18 +98,55 @@ __device__ __forceinline__ int soap_mismatches(const uint64_t *rw, int L, const 
 	return n;
 }
 
+// seed mode: mismatches of the read inside its seed [a, a + w) (count and the first two offsets, 3 = more than 2) when
+// the bases outside the seed have at most `rest_cap`, else 3; *total = all mismatches counted
+__device__ __forceinline__ int soap_seed_mismatches(const uint64_t *rw, int L, const uint64_t *dbw, int64_t gp, int a, int w,
+						    int rest_cap, int &m0, int &m1, int &total)
+{
+	int n = 0, rest = 0;
+	m0 = m1 = -1;
+	const int nw = (L + 31) >> 5;
+	for (int k = 0; k < nw; k++) {
+		uint64_t x = rw[k] ^ window64(dbw, gp + 32 * k);
+		uint64_t m = (x | (x >> 1)) & kEven;
+		if (k == nw - 1 && (L & 31))
+			m &= (1ull << (2 * (L & 31))) - 1;
+		// split the word's mismatches at the seed's bounds (bit 2 i = base 32 k + i)
+		const int lo = min(max(a - 32 * k, 0), 32), hi = min(max(a + w - 32 * k, 0), 32);
+		const uint64_t in_mask = (hi >= 32 ? ~0ull : ((1ull << (2 * hi)) - 1)) & ~(lo >= 32 ? ~0ull : ((1ull << (2 * lo)) - 1));
+		rest += __popcll(m & ~in_mask);
+		if (rest > rest_cap)
+			return 3;
+		m &= in_mask;
+		while (m) {
+			int pos = 32 * k + ((__ffsll((unsigned long long)m) - 1) >> 1);
+			m &= m - 1;
+			if (n == 0)
+				m0 = pos;
+			else if (n == 1)
+				m1 = pos;
+			if (++n > 2)
+				return 3;
+		}
+	}
+	total = n + rest;
+	return n;
+}
+
 // are read bases [a, a+16) free of mismatches at placement gp?
 __device__ __forceinline__ bool seed_exact(const uint64_t *rw, const uint64_t *dbw, int64_t gp, int a)
 {
 	return (uint32_t)window64(rw, a) == (uint32_t)window64(dbw, gp + a);
 }
 
+template <bool kSeed>
 __global__ __launch_bounds__(256) void k_soap_search(SoapView db, const uint64_t *__restrict__ fwd,
 						     const uint64_t *__restrict__ rc, const uint32_t *__restrict__ len,
 						     const uint32_t *__restrict__ woff, const uint8_t *__restrict__ skip,
 						     uint32_t n_reads, SoapHit *__restrict__ hits, unsigned long long cap,
 						     unsigned long long *__restrict__ hit_count, uint32_t *__restrict__ best_nmis,
-						     uint32_t *__restrict__ n_best, unsigned long long *__restrict__ first_hit, int mode)
+						     uint32_t *__restrict__ n_best, unsigned long long *__restrict__ first_hit, int mode,
+						     int seed_len, int rest_cap)
 {
 	const int lane = threadIdx.x & 63;
 	for (uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < n_reads; r += gridDim.x * 4) {
@@ -116,142 +160,156 @@ __global__ __launch_bounds__(256) void k_soap_search(SoapView db, const uint64_t
 			}
 			continue;
 		}
-		const bool exact_mode = L >= 48;
-		const int so[3] = { 0, L / 3, 2 * (L / 3) };
-		const int per_strand = exact_mode ? 3 : kVariants;
-		const int P = 2 * per_strand;
 		uint32_t best = 3;
-		unsigned long long slot = 0; // pass 1: where the read's next row goes
-		for (int pass = 0; pass < 2; pass++) {
-			uint32_t c0 = 0, c1 = 0, c2 = 0;
-			for (int pbase = 0; pbase < P; pbase += 64) {
-				const int pid = pbase + lane;
-				uint32_t cnt = 0, lo = 0, kmer = 0;
-				int strand = 0, sidx = 0;
-				if (pid < P) {
-					strand = pid >= per_strand;
-					sidx = pid - strand * per_strand;
-					const uint64_t *rw = (strand ? rc : fwd) + w0;
-					kmer = exact_mode ? kmer16(rw, so[sidx]) : kmer_variant(kmer16(rw, 0), sidx);
-					uint32_t b = seed_bucket(kmer, db.bits);
-					lo = db.bucket_off[b];
-					cnt = db.bucket_off[(uint64_t)b + 1] - lo;
-				}
-				uint32_t incl = cnt;
-#pragma unroll
-				for (int d = 1; d < 64; d <<= 1) {
-					uint32_t t = __shfl_up(incl, d);
-					if (lane >= d)
-						incl += t;
-				}
-				const uint32_t excl = incl - cnt, T = __shfl(incl, 63);
-				for (uint32_t it = 0; it < T; it += 64) {
-					const uint32_t item = it + lane;
-					const bool active = item < T;
-					const uint32_t key = active ? item : T - 1;
-					int o = 0;
-#pragma unroll
-					for (int step = 32; step >= 1; step >>= 1) {
-						int cand = o + step;
-						uint32_t e = __shfl(excl, cand & 63);
-						if (cand < 64 && e <= key)
-							o = cand;
+		// phase 0: the whole read; phase 1 (seed mode, a read with no whole-read placement): its seed of seed_len bases
+		for (int phase = 0; phase < (kSeed ? 2 : 1); phase++) {
+			if (kSeed && phase == 1 && (best != 3 || seed_len < kSoapMinSeed || seed_len >= L))
+				break;
+			const int W = kSeed && phase ? seed_len : L; // the window that holds at most 2 mismatches
+			const bool exact_mode = W >= 48;
+			const int so[3] = { 0, W / 3, 2 * (W / 3) };
+			const int per_strand = exact_mode ? 3 : kVariants;
+			const int P = 2 * per_strand;
+			unsigned long long slot = 0; // pass 1: where the read's next row goes
+			for (int pass = 0; pass < 2; pass++) {
+				uint32_t c0 = 0, c1 = 0, c2 = 0;
+				for (int pbase = 0; pbase < P; pbase += 64) {
+					const int pid = pbase + lane;
+					uint32_t cnt = 0, lo = 0, kmer = 0;
+					int strand = 0, sidx = 0;
+					if (pid < P) {
+						strand = pid >= per_strand;
+						sidx = pid - strand * per_strand;
+						const uint64_t *rw = (strand ? rc : fwd) + w0;
+						const int wa = kSeed && phase && strand ? L - W : 0; // '-': the seed is the reverse complement's tail
+						kmer = exact_mode ? kmer16(rw, wa + so[sidx]) : kmer_variant(kmer16(rw, wa), sidx);
+						uint32_t b = seed_bucket(kmer, db.bits);
+						lo = db.bucket_off[b];
+						cnt = db.bucket_off[(uint64_t)b + 1] - lo;
 					}
-					const uint32_t o_excl = __shfl(excl, o), o_lo = __shfl(lo, o), o_kmer = __shfl(kmer, o);
-					const int o_strand = __shfl(strand, o), o_sidx = __shfl(sidx, o);
-					int nm = 3, m0 = -1, m1 = -1;
-					int64_t gp = 0;
-					do {
-						if (!active)
-							break;
-						const uint32_t p = db.postings[o_lo + (key - o_excl)];
-						const uint64_t *rw = (o_strand ? rc : fwd) + w0;
-						const int seed_off = exact_mode ? so[o_sidx] : 0;
-						if (p < (uint32_t)seed_off)
-							break;
-						gp = (int64_t)p - seed_off;
-						// the hit must lie inside one segment and end before its last base
-						uint32_t sl = 0, sh = db.n_seg;
-						while (sh - sl > 1) {
-							uint32_t mid = sl + (sh - sl) / 2;
-							if (db.seg_lo[mid] <= gp)
-								sl = mid;
-							else
-								sh = mid;
+					uint32_t incl = cnt;
+#pragma unroll
+					for (int d = 1; d < 64; d <<= 1) {
+						uint32_t t = __shfl_up(incl, d);
+						if (lane >= d)
+							incl += t;
+					}
+					const uint32_t excl = incl - cnt, T = __shfl(incl, 63);
+					for (uint32_t it = 0; it < T; it += 64) {
+						const uint32_t item = it + lane;
+						const bool active = item < T;
+						const uint32_t key = active ? item : T - 1;
+						int o = 0;
+#pragma unroll
+						for (int step = 32; step >= 1; step >>= 1) {
+							int cand = o + step;
+							uint32_t e = __shfl(excl, cand & 63);
+							if (cand < 64 && e <= key)
+								o = cand;
 						}
-						if (db.n_seg == 0 || gp < db.seg_lo[sl] || gp + L >= (int64_t)db.seg_hi[sl])
-							break;
-						if (exact_mode) {
-							// the seed itself must match (bucket collisions) and no earlier seed may:
-							// the placement is reported through its first exact seed
-							if (!seed_exact(rw, db.words, gp, seed_off))
+						const uint32_t o_excl = __shfl(excl, o), o_lo = __shfl(lo, o), o_kmer = __shfl(kmer, o);
+						const int o_strand = __shfl(strand, o), o_sidx = __shfl(sidx, o);
+						int nm = 3, m0 = -1, m1 = -1, total = 0;
+						int64_t gp = 0;
+						do {
+							if (!active)
 								break;
-							bool earlier = false;
-							for (int j = 0; j < o_sidx; j++)
-								earlier |= seed_exact(rw, db.words, gp, so[j]);
-							if (earlier)
+							const uint32_t p = db.postings[o_lo + (key - o_excl)];
+							const uint64_t *rw = (o_strand ? rc : fwd) + w0;
+							const int wa = kSeed && phase && o_strand ? L - W : 0;
+							const int seed_off = wa + (exact_mode ? so[o_sidx] : 0);
+							if (p < (uint32_t)seed_off)
 								break;
-						} else if (kmer16(db.words, gp) != o_kmer) {
-							break;
+							gp = (int64_t)p - seed_off;
+							// the hit must lie inside one segment and end before its last base
+							uint32_t sl = 0, sh = db.n_seg;
+							while (sh - sl > 1) {
+								uint32_t mid = sl + (sh - sl) / 2;
+								if (db.seg_lo[mid] <= gp)
+									sl = mid;
+								else
+									sh = mid;
+							}
+							if (db.n_seg == 0 || gp < db.seg_lo[sl] || gp + L >= (int64_t)db.seg_hi[sl])
+								break;
+							if (exact_mode) {
+								// the seed itself must match (bucket collisions) and no earlier seed may:
+								// the placement is reported through its first exact seed
+								if (!seed_exact(rw, db.words, gp, seed_off))
+									break;
+								bool earlier = false;
+								for (int j = 0; j < o_sidx; j++)
+									earlier |= seed_exact(rw, db.words, gp, wa + so[j]);
+								if (earlier)
+									break;
+							} else if (kmer16(db.words, gp + wa) != o_kmer) {
+								break;
+							}
+							if (kSeed && phase) {
+								nm = soap_seed_mismatches(rw, L, db.words, gp, wa, W, rest_cap, m0, m1, total);
+								break;
+							}
+							nm = soap_mismatches(rw, L, db.words, gp, m0, m1);
+							// observed on the ELF, paired-end runs only: a read of exactly 32 bases is not placed where it has
+							// two mismatches that both lie in its first 20 bases
+							if (mode == 5 && L == 32 && nm == 2 && m1 < 20)
+								nm = 3;
+						} while (false);
+						if (pass == 0) {
+							c0 += nm == 0;
+							c1 += nm == 1;
+							c2 += nm == 2;
+						} else {
+							const bool emit = mode == 5 ? nm <= 2 : (uint32_t)nm == best;
+							const unsigned long long vote = __ballot(emit);
+							if (emit) {
+								uint32_t s = db.blk_subj[(uint64_t)gp >> kBlkShift];
+								while (db.seq_off[s + 1] <= (uint64_t)gp)
+									s++;
+								SoapHit h;
+								h.read = r;
+								h.subject = s;
+								h.pos = (uint32_t)(gp - db.seq_off[s]);
+								h.mis0 = m0;
+								h.mis1 = m1;
+								h.strand_nmis = ((uint32_t)o_strand << 8) | (uint32_t)nm;
+								if (kSeed && phase)
+									h.strand_nmis |= kSeededHit | ((uint32_t)total << 24);
+								const unsigned long long g = slot + (unsigned long long)__popcll(vote & ((1ull << lane) - 1));
+								if (g < cap)
+									hits[g] = h;
+							}
+							slot += (unsigned long long)__popcll(vote);
 						}
-						nm = soap_mismatches(rw, L, db.words, gp, m0, m1);
-						// observed on the ELF, paired-end runs only: a read of exactly 32 bases is not placed where it has
-						// two mismatches that both lie in its first 20 bases
-						if (mode == 5 && L == 32 && nm == 2 && m1 < 20)
-							nm = 3;
-					} while (false);
-					if (pass == 0) {
-						c0 += nm == 0;
-						c1 += nm == 1;
-						c2 += nm == 2;
-					} else {
-						const bool emit = mode == 5 ? nm <= 2 : (uint32_t)nm == best;
-						const unsigned long long vote = __ballot(emit);
-						if (emit) {
-							uint32_t s = db.blk_subj[(uint64_t)gp >> kBlkShift];
-							while (db.seq_off[s + 1] <= (uint64_t)gp)
-								s++;
-							SoapHit h;
-							h.read = r;
-							h.subject = s;
-							h.pos = (uint32_t)(gp - db.seq_off[s]);
-							h.mis0 = m0;
-							h.mis1 = m1;
-							h.strand_nmis = ((uint32_t)o_strand << 8) | (uint32_t)nm;
-							const unsigned long long g = slot + (unsigned long long)__popcll(vote & ((1ull << lane) - 1));
-							if (g < cap)
-								hits[g] = h;
-						}
-						slot += (unsigned long long)__popcll(vote);
 					}
 				}
-			}
-			if (pass == 0) {
-				for (int d = 32; d >= 1; d >>= 1) {
-					c0 += __shfl_down(c0, d);
-					c1 += __shfl_down(c1, d);
-					c2 += __shfl_down(c2, d);
+				if (pass == 0) {
+					for (int d = 32; d >= 1; d >>= 1) {
+						c0 += __shfl_down(c0, d);
+						c1 += __shfl_down(c1, d);
+						c2 += __shfl_down(c2, d);
+					}
+					c0 = __shfl(c0, 0);
+					c1 = __shfl(c1, 0);
+					c2 = __shfl(c2, 0);
+					// -M 4: the fewest mismatches any placement has; -M 0 / 1 / 2 (soap.man:73-82, observed on the ELF):
+					// the placements with exactly that many, whether or not a better one exists
+					// mode 5 (paired-end): every placement with at most two mismatches (`best` = the fewest any has)
+					if (mode == 4 || mode == 5)
+						best = c0 ? 0u : (c1 ? 1u : (c2 ? 2u : 3u));
+					else
+						best = (mode == 0 ? c0 : (mode == 1 ? c1 : c2)) ? (uint32_t)mode : 3u;
+					const uint32_t rows = mode == 5 ? c0 + c1 + c2 : (best == 0 ? c0 : (best == 1 ? c1 : (best == 2 ? c2 : 0u)));
+					if (lane == 0) {
+						best_nmis[r] = best;
+						n_best[r] = rows;
+						slot = rows ? atomicAdd(hit_count, (unsigned long long)rows) : 0ull;
+						first_hit[r] = slot;
+					}
+					slot = __shfl(slot, 0);
+					if (best == 3)
+						break;
 				}
-				c0 = __shfl(c0, 0);
-				c1 = __shfl(c1, 0);
-				c2 = __shfl(c2, 0);
-				// -M 4: the fewest mismatches any placement has; -M 0 / 1 / 2 (soap.man:73-82, observed on the ELF):
-				// the placements with exactly that many, whether or not a better one exists
-				// mode 5 (paired-end): every placement with at most two mismatches (`best` = the fewest any has)
-				if (mode == 4 || mode == 5)
-					best = c0 ? 0u : (c1 ? 1u : (c2 ? 2u : 3u));
-				else
-					best = (mode == 0 ? c0 : (mode == 1 ? c1 : c2)) ? (uint32_t)mode : 3u;
-				const uint32_t rows = mode == 5 ? c0 + c1 + c2 : (best == 0 ? c0 : (best == 1 ? c1 : (best == 2 ? c2 : 0u)));
-				if (lane == 0) {
-					best_nmis[r] = best;
-					n_best[r] = rows;
-					slot = rows ? atomicAdd(hit_count, (unsigned long long)rows) : 0ull;
-					first_hit[r] = slot;
-				}
-				slot = __shfl(slot, 0);
-				if (best == 3)
-					break;
 			}
 		}
 	}
@@ -318,11 +376,12 @@ static inline int host_base(const std::vector<uint64_t> &w, uint64_t p) { return
 // descending when one lies at or behind offset 2 s, s = 7 for reads under 32 bases, 10 under 39, else a third of the length
 static inline int pe_descending_from(int L) { return 2 * (L < 32 ? 7 : (L < 39 ? 10 : L / 3)); }
 
+// seed_len > 0: a run with -l / -v (pgx_soap_run_seeded), whose -r 0 rows end as the ELF's do
 static void soap_row(std::string &out, const std::string &name, const std::vector<int> &rd, const SoapHit &h, uint64_t nbest,
-		     const pgx_db *db, int repeat, char mate = 'a', bool paired_run = false)
+		     const pgx_db *db, int repeat, char mate = 'a', bool paired_run = false, int seed_len = 0)
 {
 	const int L = (int)rd.size();
-	const int strand = (int)(h.strand_nmis >> 8), nmis = (int)(h.strand_nmis & 255);
+	const int strand = (int)((h.strand_nmis >> 8) & 1), nmis = (int)(h.strand_nmis & 255);
 	out += name;
 	out += '\t';
 	for (int k = 0; k < L; k++)
@@ -337,14 +396,34 @@ static void soap_row(std::string &out, const std::string &name, const std::vecto
 	snprintf(buf, sizeof buf, "\t%u\t%d", h.pos + 1, nmis);
 	out += buf;
 	const uint64_t g0 = (uint64_t)db->h_seq_off[h.subject] + h.pos;
-	int m[2] = { h.mis0, h.mis1 };
-	if (nmis == 2 && m[1] >= (paired_run ? pe_descending_from(L) : L - 13))
-		std::swap(m[0], m[1]); // single-end: entries descend when one lies in the last 13 bases
+	int m[2] = { h.mis0, h.mis1 }; // reference-oriented offsets
+	int shown[2] = { h.mis0, h.mis1 }; // the offsets the row prints
+	int q[2] = { 40, 40 };
+	if (h.strand_nmis & kSeededHit) {
+		// placed by its seed (observed on the ELF, tests/golden/soap_seed): the seed's entries, counted from the seed's
+		// reference-oriented start (rel) or from the read's: one entry -> rel in the seed's first half; two -> descending
+		// (both from the read's start) when one lies in the seed's last 13 bases, else the first from the seed's start
+		const int l = seed_len, a = strand ? L - l : 0;
+		if (nmis == 1) {
+			shown[0] = m[0] - a < l / 2 ? m[0] - a : m[0];
+			q[0] = strand && m[0] == a ? -64 : 40;
+		} else if (nmis == 2 && m[1] - a >= l - 13) {
+			std::swap(m[0], m[1]);
+			std::swap(shown[0], shown[1]);
+		} else if (nmis == 2) {
+			shown[0] = m[0] - a;
+		}
+	} else {
+		if (nmis == 2 && m[1] >= (paired_run ? pe_descending_from(L) : L - 13)) {
+			std::swap(m[0], m[1]); // single-end: entries descend when one lies in the last 13 bases
+			std::swap(shown[0], shown[1]);
+		}
+		q[0] = (nmis == 1 && strand && m[0] == 0) ? -64 : 40;
+	}
 	for (int k = 0; k < nmis; k++) {
-		const int q = (nmis == 1 && strand && m[k] == 0) ? -64 : 40;
 		// the ELF keeps the offset in 8 bits and fetches the read base through it
-		snprintf(buf, sizeof buf, "\t%c->%d%c%d", kLetters[host_base(db->h_words, g0 + (uint64_t)m[k])], m[k] & 255,
-			 kLetters[rd[(size_t)(m[k] & 255)]], q);
+		snprintf(buf, sizeof buf, "\t%c->%d%c%d", kLetters[host_base(db->h_words, g0 + (uint64_t)m[k])], shown[k] & 255,
+			 kLetters[rd[(size_t)(shown[k] & 255)]], q[k]);
 		out += buf;
 	}
 	snprintf(buf, sizeof buf, "\t%dM\t", L);
@@ -363,7 +442,7 @@ static void soap_row(std::string &out, const std::string &name, const std::vecto
 		run = 0;
 		first = false;
 	}
-	if (run > 0 || repeat != 1 || first)
+	if (run > 0 || first || (seed_len > 0 ? repeat == 2 : repeat != 1))
 		out += std::to_string(run);
 	out += '\n';
 }
@@ -469,7 +548,8 @@ struct SoapSearch {
 	}
 };
 
-static int soap_search(const SoapDb &sd, const char *reads_path, int max_n, int mode, SoapSearch &s)
+// seed_len > 0: seed mode (pgx_soap_run_seeded), a read with no whole-read placement is placed by its seed
+static int soap_search(const SoapDb &sd, const char *reads_path, int max_n, int mode, SoapSearch &s, int seed_len = 0, int rest_cap = 0)
 {
 	PGX_TRY(reads_from_fasta_ex(reads_path, 0, -1, true, &s.nn, &s.rd));
 	const size_t n = (size_t)s.rd->n;
@@ -497,9 +577,14 @@ static int soap_search(const SoapDb &sd, const char *reads_path, int max_n, int 
 		if (hipMemset(d_count.data(), 0, sizeof(unsigned long long)) != hipSuccess)
 			return fail(PGX_E_NODEVICE, "hipMemset failed");
 		const int grid = (int)std::min<uint64_t>((n + 3) / 4, 2048);
-		hipLaunchKernelGGL(k_soap_search, dim3(grid), dim3(256), 0, 0, sd.v, s.rd->d_fwd.data(), s.rd->d_rc.data(), s.rd->d_len.data(),
-				   s.rd->d_woff.data(), d_skip.data(), (uint32_t)n, s.d_hits.data(), (unsigned long long)cap, d_count.data(),
-				   s.d_best.data(), s.d_nbest.data(), s.d_first.data(), mode);
+		if (seed_len > 0)
+			hipLaunchKernelGGL(k_soap_search<true>, dim3(grid), dim3(256), 0, 0, sd.v, s.rd->d_fwd.data(), s.rd->d_rc.data(),
+					   s.rd->d_len.data(), s.rd->d_woff.data(), d_skip.data(), (uint32_t)n, s.d_hits.data(), (unsigned long long)cap,
+					   d_count.data(), s.d_best.data(), s.d_nbest.data(), s.d_first.data(), mode, seed_len, rest_cap);
+		else
+			hipLaunchKernelGGL(k_soap_search<false>, dim3(grid), dim3(256), 0, 0, sd.v, s.rd->d_fwd.data(), s.rd->d_rc.data(),
+					   s.rd->d_len.data(), s.rd->d_woff.data(), d_skip.data(), (uint32_t)n, s.d_hits.data(), (unsigned long long)cap,
+					   d_count.data(), s.d_best.data(), s.d_nbest.data(), s.d_first.data(), mode, 0, 0);
 		if (hipGetLastError() != hipSuccess)
 			return fail(PGX_E_NODEVICE, "k_soap_search launch failed");
 		PGX_TRY(d_count.download(&total, 1));
@@ -519,16 +604,17 @@ static int soap_search(const SoapDb &sd, const char *reads_path, int max_n, int 
 				  [](const SoapHit &a, const SoapHit &b) {
 					  if (a.subject != b.subject) return a.subject < b.subject;
 					  if (a.pos != b.pos) return a.pos < b.pos;
-					  return (a.strand_nmis >> 8) < (b.strand_nmis >> 8);
+					  return ((a.strand_nmis >> 8) & 1) < ((b.strand_nmis >> 8) & 1);
 				  });
 	return 0;
 }
 
-static int soap_run_single(const pgx_soap_opts *o, const SoapDb &sd)
+// seed_len > 0: a run with -l / -v (the ELF's rules for -r 0 too: a read it does not print goes to the unmapped file)
+static int soap_run_single(const pgx_soap_opts *o, const SoapDb &sd, int seed_len = 0, int rest_cap = 0)
 {
 	SoapSearch s;
-	PGX_TRY(soap_search(sd, o->reads_path, o->max_n, o->match_mode, s));
-	if (o->match_mode != 4 && s.rd->max_len > 256)
+	PGX_TRY(soap_search(sd, o->reads_path, o->max_n, o->match_mode, s, seed_len, rest_cap));
+	if (seed_len == 0 && o->match_mode != 4 && s.rd->max_len > 256)
 		// for reads above -l (256) the ELF applies -M 0 / 1 / 2 to the first 256 bases only: not restated
 		return fail(PGX_E_LIMIT, "soap: -M %d is implemented for reads of at most 256 bases (this file holds one of %d)", o->match_mode,
 			    (int)s.rd->max_len);
@@ -543,10 +629,10 @@ static int soap_run_single(const pgx_soap_opts *o, const SoapDb &sd)
 			const uint32_t lim = o->repeat_mode == 2 ? nb : 1;
 			for (uint32_t x = 0; x < lim; x++)
 				soap_row(out, o->report_id ? std::to_string(r) : s.rd->name_of(r), // -t: the read's 0-based ordinal in the file
-					 (h[x].strand_nmis >> 8) ? s.rv : s.fw, h[x], nb, sd.db, o->repeat_mode);
+					 ((h[x].strand_nmis >> 8) & 1) ? s.rv : s.fw, h[x], nb, sd.db, o->repeat_mode, 'a', false, seed_len);
 			printed = true;
 		}
-		if (!printed && nb <= 1)
+		if (!printed && (nb <= 1 || seed_len > 0))
 			s.unmapped(unm, r);
 	}
 	PGX_TRY(write_text_file(o->out_path, out));
@@ -667,5 +753,24 @@ int pgx_soap_run(const pgx_soap_opts *o)
 	SoapDb sd;
 	PGX_TRY(soap_db_open(o->db_prefix, sd));
 	return o->reads_b_path && *o->reads_b_path ? soap_run_paired(o, sd) : soap_run_single(o, sd);
+}
+
+int pgx_soap_run_seeded(const pgx_soap_opts *o, int seed_len, int max_total_mis)
+{
+	if (!o || !o->reads_path || !o->db_prefix || !o->out_path)
+		return fail(PGX_E_ARG, "soap: -a, -D and -o are required");
+	if (o->match_mode != 4 && (o->match_mode < 0 || o->match_mode > 2))
+		return fail(PGX_E_ARG, "soap: -M must be 0, 1, 2 or 4");
+	if (o->repeat_mode < 0 || o->repeat_mode > 2)
+		return fail(PGX_E_ARG, "soap: -r must be 0, 1 or 2");
+	if (seed_len < 1 || max_total_mis < 0)
+		return fail(PGX_E_ARG, "soap: -l must be positive and -v not negative");
+	if (o->reads_b_path && *o->reads_b_path)
+		return fail(PGX_E_LIMIT, "soap: -l / -v are implemented for single-end runs (not with -b)");
+	PGX_TRY(require_device());
+	SoapDb sd;
+	PGX_TRY(soap_db_open(o->db_prefix, sd));
+	// -l under 27 places reads whole; -v above 20 counts as 20 (observed on the ELF, tests/golden/soap_seed)
+	return soap_run_single(o, sd, seed_len, std::min(max_total_mis, kSoapMaxRest));
 }
 }
