@@ -1813,15 +1813,14 @@ static DbView db_view(const pgx_db *db)
 	v.blk_subj = db->d_blk_subj.data();
 	v.blk_info = db->d_blk_info.data();
 	v.post_ctx = db->d_post_ctx.data();
-	static const bool no_amb_blk = getenv("PGX_NO_AMB_BLK") != nullptr; // (measurement aid, read once per process)
-	v.amb_blk = db->has_amb && !no_amb_blk ? db->d_amb_blk.data() : nullptr;
+	v.amb_blk = db->has_amb ? db->d_amb_blk.data() : nullptr;
 	v.bucket_off = db->d_bucket_off.data();
 	v.postings = db->d_postings.data();
 	v.n_seq = (uint32_t)db->n_seq;
 	v.n_bases = db->n_bases;
 	v.bits = db->index_bits;
 	v.gapped = db->ungapped ? 0 : 1;
-	v.deep_from = gapped_deep_from();
+	v.deep_from = kGapDeepFrom;
 #ifdef PGX_STAGE_PROBES
 	v.dbg_stop = getenv("PGX_SEED_STOP") ? atoi(getenv("PGX_SEED_STOP")) : 0; // (measurement builds: the kernel truncated after a stage)
 #else

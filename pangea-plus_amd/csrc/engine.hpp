@@ -274,8 +274,8 @@ constexpr uint32_t kFragmented = 0xFFFFFFFFu; // read_start of a read whose hits
 struct GappedWork {
 	DevBuf<unsigned long long> big_list, big_list2; // HSPs for the one-wavefront-per-HSP kernel; those of them that need its large rows
 	DevBuf<uint32_t> big_count; // [0] entries appended (may exceed the capacity: the caller grows and repeats), [1] of the second list
-	DevBuf<uint2> side_main, side_ovf, side_list; // per table slot (per list entry, second tier): the left side's extension, parked until the right side is done
-	DevBuf<uint32_t> order;            // per block of k_gapped_fast: the pool's HSPs in cost order
+	DevBuf<uint2> side_list; // per list entry of k_gapped_list: the left side's extension, parked until the right side is done
+	DevBuf<uint32_t> order;            // per block of k_gapped_pool / k_gapped_list: its HSPs in cost order
 	DevBuf<uint32_t> items, bins;      // binned form: the main table's slots in (region, bin) order; histograms, cursors, total
 	DevBuf<uint32_t> items1;           // ... in region order (first pass), with their key bytes
 	DevBuf<uint8_t> keys1;
@@ -283,16 +283,8 @@ struct GappedWork {
 int gapped_stage(const DbView &dv, const ReadsView &rv, pgx_hit *main_table, const uint8_t *main_key, const uint32_t *read_start,
 		 const uint32_t *read_cnt, pgx_hit *ovf_table, const uint8_t *ovf_key, const unsigned long long *ovf_count, unsigned long long ovf_cap, bool long_reads,
 		 unsigned long long hit_cap, int max_len, GappedWork &gw, hipStream_t stream, const unsigned long long *main_used, const uint8_t *main_reg);
-// reads longer than this many bases run the gapped stage's rows for 40 differences a side (PGX_GAP_DEEP_FROM: measurement aid)
-inline int gapped_deep_from()
-{
-	static const int v = [] {
-		const char *e = getenv("PGX_GAP_DEEP_FROM");
-		const int x = e ? atoi(e) : 320;
-		return x < 192 ? 192 : (x > 320 ? 320 : x);
-	}();
-	return v;
-}
+// reads longer than this many bases run the gapped stage's rows for 40 differences a side
+constexpr int kGapDeepFrom = 320;
 // the main table's HSPs are handled region by region of the database (at most 240 regions: positions >> this)
 inline int gapped_region_shift(int64_t n_bases)
 {

@@ -20,13 +20,12 @@
 //                  X-drop history in a register ring (greedy_rows_deep)
 //   k_gapped_pool<FLAT, ...>         the overflow table and batches of long reads: a wavefront orders a pool of HSPs by the
 //                  key byte itself, then gap_round
-//   k_gapped_fast<2, MAXL, WAVES, 18> / <2, 512, 2, 40>   the LISTS behind the lean tier: rows with the full statistics in
+//   k_gapped_list<MAXL, WAVES, 18> / <512, 2, 40>   the LISTS behind the lean tier: rows with the full statistics in
 //                  the cell (mismatches, gap openings, open-gap kind) for 18, then 40 differences with the X-drop history
 //   k_gapped_diag  one WAVEFRONT per listed HSP, one lane per diagonal, the level in one register per lane, neighbours by
 //                  DPP wave shifts: reads above 512 bases and what the lane-per-HSP tiers pass on
 //   k_gapped_big<62>, <1000>   one wavefront per listed HSP, rows double-buffered in LDS, ambiguity flags: what
 //                  k_gapped_diag hands on (drift beyond its 64 lanes, ambiguity letters, reads above 2 048 bases)
-// (k_gapped_fast<0|1>, round 2's two-pass pools over the tables, is compiled in measurement builds only: PGX_STAGE_PROBES.)
 // Every tier cuts a cell whose score could not pass the best one even if every remaining letter matched.  The cut cannot
 // change the result (a child's bound is below its parent's, so no surviving cell has a cut parent; a cut cell never holds
 // the best score), which is why the sequential kernel, the parallel ones (bound taken one step late) and the checker (no
@@ -47,20 +46,6 @@ constexpr int kGUnrollLevels = 7; // levels of the lane kernel compiled as strai
 constexpr uint32_t kCellNone = 0x80000000u; // lane kernel: a dead cell holds i = -32768
 constexpr uint32_t kBigNone = 0xFFFFFFFFu;  // wide kernel: a dead cell
 static_assert(kGFastD < kGLag, "the first tier keeps no score history");
-
-#ifdef PGX_STAGE_PROBES
-// measurement builds: [0] cell steps of a wavefront, [1] cells evaluated by lanes, [2] slide rounds (wavefront) inside cell
-// steps, [3] levels, [4] rounds (sides x 64), [5] lanes with a side, [6] walk rounds of B0, [7] lane-cells alive at level start
-__device__ unsigned long long g_gap_stats[8];
-#define GAP_STAT(i, n)                                          \
-	do {                                                    \
-		const unsigned long long n_ = (unsigned long long)(n); /* (ballots are taken by the whole wavefront) */ \
-		if ((threadIdx.x & 63) == 0)                    \
-			atomicAdd(&g_gap_stats[i], n_);         \
-	} while (0)
-#else
-#define GAP_STAT(i, n) ((void)0)
-#endif
 
 // compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
 template <int B, int E, class F> __device__ __forceinline__ void static_for(F &&f)
@@ -141,7 +126,7 @@ __device__ __forceinline__ uint32_t scan_low(uint32_t y)
 // Letters that match from read position qp / window position dp on (positions as BIT offsets, 2 per letter: the funnel
 // shift takes its amount from the low five bits as they are), at most min(16, cap).  Letters past `cap` are whatever the
 // window holds: the unsigned minimum drops them, and turns "no mismatch" (-1 from the bit scan) into the cap.
-// Only ascending: the side LEFT of the anchor is staged reversed (see k_gapped_fast), so one copy of the row code serves
+// Only ascending: the side LEFT of the anchor is staged reversed (see k_gapped_list), so one copy of the row code serves
 // both sides -- half the instruction footprint of the kernel.
 // (the list tiers' letters lie in TRANSPOSED rows too since round 3: word i of a lane at w[i * 64], its own LDS bank)
 constexpr int kLaneWordStride = 64;
@@ -247,14 +232,9 @@ __device__ __forceinline__ void write_gapped(pgx_hit *hp, const pgx_hit &h, cons
 template <int D>
 __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t *dbwin, int *xring, bool on, int q0, int d0, int M, int N, int b0, Side &out)
 {
-	int slide_rounds = 0;
-	(void)slide_rounds;
 	const int q0b = 2 * q0, d0b = 2 * d0; // bit offsets of the side's first letters
 	auto slide = [&](int &ii, int &jj) {
 		for (;;) {
-#ifdef PGX_STAGE_PROBES
-			slide_rounds++;
-#endif
 			const int cap = M - ii < N - jj ? M - ii : N - jj;
 			if (cap <= 0)
 				break;
@@ -267,8 +247,6 @@ __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t 
 	};
 	out.i = out.j = out.s2 = out.mism = out.gopen = 0;
 	int i0 = 0, j0 = 0;
-	GAP_STAT(4, 1);
-	GAP_STAT(5, __popcll(__ballot(on)));
 	if (on)
 		slide(i0, j0);
 	out.i = out.j = i0;
@@ -333,11 +311,6 @@ __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t 
 		if constexpr (D >= kGLag)
 			alive = alive & (v + jj0 - six_d >= tcmp); // the X-drop test on the score before sliding (tcmp = T[d - 19] - 2 X)
 		uint32_t nc = kCellNone;
-		GAP_STAT(0, 1);
-		GAP_STAT(1, __popcll(__ballot(alive)));
-#ifdef PGX_STAGE_PROBES
-		slide_rounds = 0;
-#endif
 		if (alive) {
 			// the first 16 letters without the loop's bookkeeping: off the anchor's diagonal a run rarely goes further
 			int ii = v, jj = jj0;
@@ -365,16 +338,6 @@ __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t 
 			slack_s = B2 - best;
 			any = true;
 		}
-#ifdef PGX_STAGE_PROBES
-		{
-			int mx = alive ? slide_rounds : 0;
-			for (int sh = 1; sh < 64; sh <<= 1) {
-				const int o = __shfl_xor(mx, sh);
-				mx = o > mx ? o : mx;
-			}
-			GAP_STAT(2, mx);
-		}
-#endif
 		prev = cur;
 		R[c] = nc;
 	};
@@ -398,8 +361,6 @@ __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t 
 			} else {
 				prev = kCellNone;
 				any = false;
-				GAP_STAT(3, 1);
-				GAP_STAT(7, __popcll(__ballot(live)));
 				static_for<C - d, C + d + 1>([&](auto cc) { cell(cc, 6 * d, std::integral_constant<int, d - 1>{}); });
 				live = any && more(d);
 				if constexpr (D >= kGLag)
@@ -416,8 +377,6 @@ __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t 
 			tcmp = d >= kGLag ? xring[d - kGLag] - kGX2 : -(1 << 29);
 		prev = kCellNone;
 		any = false;
-		GAP_STAT(3, 1);
-		GAP_STAT(7, __popcll(__ballot(live)));
 		const int six_d = 6 * d;
 		static_for<0, (kCells - 2 + kGGroup - 1) / kGGroup>([&](auto gc) {
 			constexpr int c0 = 1 + decltype(gc)::value * kGGroup;
@@ -478,13 +437,8 @@ __device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c)
 	return r;
 }
 
-#ifndef PGX_LEAN_GROUP
-#define PGX_LEAN_GROUP 2
-#endif
-#ifndef PGX_LEAN_WAVES
-#define PGX_LEAN_WAVES 4
-#endif
-constexpr int kLeanGroup = PGX_LEAN_GROUP; // cells computed as one piece of straight code (their LDS reads in flight together)
+constexpr int kLeanGroup = 2; // cells computed as one piece of straight code (their LDS reads in flight together)
+constexpr int kLeanWaves = 4; // wavefronts per SIMD of the tiers for reads of <= 160 bases
 constexpr uint32_t kLeanDead = 0xFFF80000u; // i = -4
 constexpr uint32_t kLeanFromCur = 0x28000u;  // i + 1, priority 2 (a mismatch on this diagonal)
 constexpr uint32_t kLeanFromPrev = 0x24001u; // i + 1, priority 1, one more gap column in the subject row (from k - 1)
@@ -999,15 +953,13 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 constexpr int kBlkItems = 2048; // HSPs a wavefront orders at a time
 constexpr int kKeyBuckets = 16;  // mismatches of the diagonal on one side of the seed run, capped at 15
 
-template <int MAXL, int D, bool LEAN> struct FastLds {
+template <int MAXL, int D> struct ListLds {
 	static constexpr int kRd = MAXL / 16 + 2;                    // read strand, 16 bases per word
 	static constexpr int kDb = (MAXL + 2 * D + 48 + 15) / 16 + 1; // database window
 	static constexpr int kSeq = (kRd + kDb) | 1; // odd stride: lanes that use the same index hit different banks
 	static constexpr int kRing = D >= kGLag ? ((D - kGLag + 2) | 1) : 1; // the X-drop history of a lane (second tier)
-	static constexpr bool kLean = LEAN; // first tier: TRANSPOSED rows (row r of lane l at seq[r * 64 + l]), spare rows in front
-	static constexpr int kRows = kLeanFrontRows + kRd + kDb;
-	uint32_t seq[kLean ? kRows * 64 : 64 * kSeq];
-	int xring[D >= kGLag ? 64 : 0][kRing]; // (nothing in the first tier: 256 bytes more there cost a fifth wavefront its LDS)
+	uint32_t seq[64 * kSeq];
+	int xring[D >= kGLag ? 64 : 0][kRing]; // (none below kGLag differences: no X-drop test is due there)
 	uint32_t bucket[kKeyBuckets];
 	// (the pool's HSPs in cost order live in GLOBAL scratch, one array per block: with them here the kernel held 12.6 KB of
 	// LDS per wavefront = 3 wavefronts per SIMD; without, 8.5 KB = 4, and a wavefront of this kernel is bound by its own
@@ -1053,110 +1005,50 @@ __device__ __forceinline__ void list_append(bool fail, pgx_hit *hp, unsigned lon
 	}
 }
 
-// FLAT: the table is a flat array of *count hits (overflow table); otherwise the hits of read r are the read_cnt[r] records
-// from read_start[r] of the seed stage's main table (kFragmented: they are in the overflow table).
-// A wavefront takes the HSPs of 64 reads (at most kBlkItems at a time), orders them by the seed stage's work estimate
-// (a counting sort in LDS), and runs them 64 at a time: lanes of one round have about the same number of rows.
-// MODE 0: the reads' pools of the main table; 1 (FLAT): the overflow table; 2 (LIST): the HSPs the first tier listed, as
-// pointers to their seed records (`table` = the list as pgx_hit **; a side's result is parked by list position).
-// D: differences per side (18 first tier, 40 second tier, which makes the X-drop tests).
-template <int MODE, int MAXL, int WAVES, int D>
-// (WAVES per SIMD: 4 = 128 registers -- the row is 39 of them; the compiler parks three values in scratch around the rows;
-// 5 = 96 registers, 24 values in scratch, for reads of <= 160 bases whose staged letters fit 7.5 KB of LDS: worth 6 % once
-// the grid is two full rounds of resident wavefronts -- with 8 192 blocks on 5 120 slots the second round ran at 60 %)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) void k_gapped_fast(GapView v, pgx_hit *__restrict__ table, unsigned long long table_cap,
-						     const uint32_t *__restrict__ read_start, const uint32_t *__restrict__ read_cnt,
-						     uint32_t n_reads, const unsigned long long *__restrict__ flat_count,
+// The tiers behind the lean rows, over LISTS: a list entry points at the seed record of an HSP that the tier before
+// could not finish.  A wavefront takes 64 or 512 entries, orders them by the level estimate of a side (a counting sort
+// in LDS) and runs them 64 at a time, so that the lanes of one round have about the same number of rows.  A side's
+// result is parked by list position in `side_res`.
+// D: differences per side (18 for what the lean rows listed, 40 behind that, with the X-drop tests).
+template <int MAXL, int WAVES, int D>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) void k_gapped_list(GapView v, pgx_hit *const *__restrict__ list, unsigned long long list_cap,
+						     const uint32_t *__restrict__ count,
 						     unsigned long long *__restrict__ big_list, uint32_t *__restrict__ big_count, uint32_t big_cap,
-						     uint2 *__restrict__ side_res, int dbg, uint32_t *__restrict__ order_all)
+						     uint2 *__restrict__ side_res, uint32_t *__restrict__ order_all)
 {
-	constexpr bool FLAT = MODE != 0, LIST = MODE == 2;
-	constexpr bool LEAN = MODE != 2 && D < kGLag; // the first tier over the tables; over a list: the rows with the full statistics
-	using Lds = FastLds<MAXL, D, LEAN>;
+	using Lds = ListLds<MAXL, D>;
 	__shared__ Lds lds;
 	uint32_t *order = order_all + (size_t)blockIdx.x * kBlkItems; // written and read by this wavefront only, through L2
 	const int lane = threadIdx.x & 63;
 	// word w of the lane's staged read letters / database window
-	uint32_t *rdw = LEAN ? &lds.seq[kLeanFrontRows * 64 + lane] : &lds.seq[lane];
+	uint32_t *rdw = &lds.seq[lane];
 	uint32_t *dbwin = rdw + Lds::kRd * 64;
 	constexpr int WS = kLaneWordStride; // stride of a lane's words (row r of lane l at seq[r * 64 + l])
-	const unsigned long long n_flat_raw = FLAT ? (LIST ? (unsigned long long)*reinterpret_cast<const uint32_t *>(flat_count) : *flat_count) : 0ull;
-	const unsigned long long n_flat = n_flat_raw < table_cap ? n_flat_raw : table_cap;
+	const unsigned long long n_raw = *count;
+	const unsigned long long n_list = n_raw < list_cap ? n_raw : list_cap;
 	// (with 2 048 entries per block the few listed HSPs of a short-read batch all fell to one or two wavefronts)
-	// (LIST: 64 entries, one round a side, per block while the list is short, so that its HSPs spread over the chip; 512 --
+	// (64 entries, one round a side, per block while the list is short, so that its HSPs spread over the chip; 512 --
 	// eight rounds ordered by the level estimate -- once there are enough of them to fill it several times over)
-	const unsigned long long kItems = LIST ? (n_flat > 64ull * 4ull * gridDim.x ? 512ull : 64ull) : (unsigned long long)kBlkItems;
-	const unsigned long long n_blocks = FLAT ? (n_flat + kItems - 1) / kItems : ((unsigned long long)n_reads + 63ull) / 64ull;
+	const unsigned long long kItems = n_list > 64ull * 4ull * gridDim.x ? 512ull : 64ull;
+	const unsigned long long n_blocks = (n_list + kItems - 1) / kItems;
 
-	// LEAN: the HSPs to hand on wait in the two spare rows in front of the letters (128 table slots; what a dead cell reads
-	// there is never used) and go to the list 64-128 at a time
-	uint32_t n_pend = 0;
-	auto flush_pend = [&]() {
-		if constexpr (LEAN) {
-			for (uint32_t e0 = 0; e0 < n_pend; e0 += 64) {
-				const bool mine = e0 + lane < n_pend;
-				pgx_hit *hp = table + (mine ? lds.seq[e0 + lane] : 0u);
-				list_append(mine, hp, big_list, big_count, big_cap);
-			}
-			n_pend = 0;
-			lds_sync();
-		}
-	};
 	for (unsigned long long blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-		uint32_t excl = 0, st = 0, T;
-		if (FLAT) {
-			const unsigned long long left = n_flat - blk * kItems;
-			T = (uint32_t)(left < kItems ? left : kItems);
-		} else {
-			const uint32_t r = (uint32_t)blk * 64u + lane;
-			uint32_t cnt = 0;
-			if (r < n_reads) {
-				st = read_start[r];
-				cnt = st == kFragmented ? 0u : read_cnt[r];
-				if ((unsigned long long)st + cnt > table_cap)
-					cnt = 0; // the table was too small for this read: the host repeats the step with a larger one
-			}
-			uint32_t incl = cnt;
-#pragma unroll
-			for (int dd = 1; dd < 64; dd <<= 1) {
-				const uint32_t t = __shfl_up(incl, dd);
-				if (lane >= dd)
-					incl += t;
-			}
-			excl = incl - cnt;
-			T = __shfl(incl, 63);
-		}
-		// the bucket of an HSP's side: the seed stage's level estimate (first tier: the key byte of its slot; second tier:
-		// the record's own columns, whose estimates are not cut at 15, moved down so that 16 .. 31 spread over the buckets)
+		const unsigned long long left = n_list - blk * kItems;
+		const uint32_t T = (uint32_t)(left < kItems ? left : kItems);
+		// the bucket of an HSP's side: its level estimate
 		auto key_of = [&](const pgx_hit *p, int side) -> uint32_t {
-			if (LIST && D < kGLag)
+			if constexpr (D < kGLag) {
 				return (uint32_t)(side ? p->gapopen : p->mismatch) & 15u; // (the HSPs the lean tier listed: its own estimates)
-			if (LIST) {
+			} else {
 				// the record's own estimates are cut at 15, where this tier's sides begin: the levels again from the record's
 				// B0 and the side's letters, floor((2 M - B0) / 5), 16 .. 31 spread over the buckets
 				const int anchor = p->qend, L = p->score, b0 = side ? (p->send >> 12) & 0x7FF : (p->send >> 1) & 0x7FF;
 				const int lv = (2 * (side ? L - anchor : anchor) - b0) / 5 - 16;
 				return (uint32_t)(b0 == 0 || lv > 15 ? 15 : (lv < 0 ? 0 : lv));
 			}
-			return (uint32_t)(v.key[p - table] >> (4 * side)) & 15u;
 		};
 		// item -> its record
-		auto locate = [&](uint32_t item) -> pgx_hit * {
-			if (LIST)
-				return reinterpret_cast<pgx_hit *const *>(table)[blk * kItems + item];
-			if (FLAT)
-				return table + blk * kItems + item;
-			int o = 0;
-#pragma unroll
-			for (int step = 32; step >= 1; step >>= 1) {
-				const int cand = o + step;
-				const uint32_t e = __shfl(excl, cand & 63);
-				if (cand < 64 && e <= item)
-					o = cand;
-			}
-			const uint32_t base = __shfl(st, o), ex = __shfl(excl, o);
-			return table + base + (item - ex);
-		};
+		auto locate = [&](uint32_t item) -> pgx_hit * { return list[blk * kItems + item]; };
 		for (uint32_t chunk = 0; chunk < T; chunk += kBlkItems) {
 			const uint32_t n_it = T - chunk < (uint32_t)kBlkItems ? T - chunk : (uint32_t)kBlkItems;
 			// The two sides of an HSP cost differently (rows ~ 1.2 x the mismatches of the diagonal on that side), so they
@@ -1202,7 +1094,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 					const bool mine = it + lane < n_it;
 					const uint32_t item = __hip_atomic_load(&order[mine ? it + lane : n_it - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 					pgx_hit *hp = locate(chunk + item);
-					const size_t slot = LIST ? (size_t)(blk * kItems + chunk + item) : (size_t)(hp - table);
+					const size_t slot = (size_t)(blk * kItems + chunk + item);
 					pgx_hit h;
 					h.read = h.subject = h.qstart = h.qend = h.sstart = h.send = h.score = 0;
 					h.mismatch = h.gapopen = 0;
@@ -1272,14 +1164,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 					}
 					lds_sync();
 					Side sd;
-					bool ok;
-					if constexpr (LEAN) {
-						// (a side whose best cell holds two or more gap columns goes on: the next tier carries the statistics)
-						ok = greedy_rows_lean<D>((const lds_word *)&lds.seq[0], (uint32_t)lane * 4u, on, 32 * kLeanFrontRows + 2 * sq0, 32 * (kLeanFrontRows + Lds::kRd) + 2 * sd0,
-									  side ? a.L - a.qa : a.qa, side ? a.slen - a.sa : a.sa, side ? a.b0r : a.b0l, sd) == 0;
-					} else {
-						ok = greedy_rows<D>(rdw, dbwin, D >= kGLag ? &lds.xring[D >= kGLag ? lane : 0][0] : nullptr, on, sq0, sd0, side ? a.L - a.qa : a.qa, side ? a.slen - a.sa : a.sa, side ? a.b0r : a.b0l, sd);
-					}
+					const bool ok = greedy_rows<D>(rdw, dbwin, D >= kGLag ? &lds.xring[D >= kGLag ? lane : 0][0] : nullptr, on, sq0, sd0, side ? a.L - a.qa : a.qa,
+								       side ? a.slen - a.sa : a.sa, side ? a.b0r : a.b0l, sd);
 					if (mine) {
 						if (side == 0) {
 							// parked: i | j << 10 | mismatches << 20 | gap openings << 26 ; gap columns | wide << 31
@@ -1296,36 +1182,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 							write_gapped(hp, h, a, l, sd);
 						}
 					}
-					if (side == 1) {
-						const bool fail = mine && !(on && ok);
-						if constexpr (LEAN) {
-							const unsigned long long fm = __ballot(fail);
-							if (fm != 0ull) {
-								lds_sync(); // (the rows' last reads of the front rows are done)
-								if (fail)
-									lds.seq[n_pend + (uint32_t)__popcll(fm & ((1ull << lane) - 1ull))] = (uint32_t)(hp - table);
-								n_pend += (uint32_t)__popcll(fm);
-								lds_sync();
-								if (n_pend > 64u)
-									flush_pend();
-							}
-						} else {
-							list_append(fail, hp, big_list, big_count, big_cap);
-						}
-					}
+					if (side == 1)
+						list_append(mine && !(on && ok), hp, big_list, big_count, big_cap);
 					lds_sync();
 				}
 			}
 		}
-		flush_pend();
 	}
 }
 
 // ------------------------------------------------------------------------------------------ the main table, binned
 // Round 3, second finding.  With the lean rows the stage did NOT get faster: PMC (profiles/r03_*) shows what holds it --
 // 209 L2 misses per read (7.4 per HSP) at 39 G misses a second, 0.78 of what the chip delivers for random 64-byte lines
-// (pgx_probe_gather: 50 G/s).  The pool-per-wavefront form above touches every record three times (ordering, left pass,
-// right pass), parks the left result, and fetches an HSP's letters twice.  This form touches them ONCE:
+// (pgx_probe_gather: 50 G/s).  Round 2's pool-per-wavefront form touched every record three times (ordering, left pass,
+// right pass), parked the left result, and fetched an HSP's letters twice.  This form touches them ONCE:
 //   1. k_gap_hist / k_gap_bins / k_gap_scatter: a counting sort of the main table's SLOT NUMBERS by the seed stage's key
 //      byte (levels left | levels right << 4; 0xFF = no record there), streaming over the 1-byte keys only: 256 bins, the
 //      costliest first.  Every HSP of a bin runs the same number of levels on BOTH sides.
@@ -1936,20 +1806,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 	}
 }
 
-#ifdef PGX_STAGE_PROBES
-} // namespace pgx
-extern "C" int pgx_gap_stats(unsigned long long *out, int reset) // measurement builds only (tools/probe_gapstats.py)
-{
-	unsigned long long z[8] = { 0 };
-	if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(pgx::g_gap_stats), sizeof z) != hipSuccess)
-		return -1;
-	if (reset && hipMemcpyToSymbol(HIP_SYMBOL(pgx::g_gap_stats), z, sizeof z) != hipSuccess)
-		return -1;
-	return 0;
-}
-namespace pgx {
-#endif
-
 // ------------------------------------------------------------------------------------------ one wavefront per HSP
 // cell: x = i, y = mismatches | gap openings << 12 | kind << 24 | matched-after << 26
 // DMAX = differences per side this instance can hold: 62 (the diagonals of a level fit one wavefront, 2 KB of LDS: 32
@@ -2431,24 +2287,12 @@ int gapped_stage(const DbView &dv, const ReadsView &rv, pgx_hit *main_table, con
 	const uint32_t big_cap = (uint32_t)std::min<unsigned long long>(want, 0xFFFFFFF0ull);
 	PGX_TRY(gw.big_list.ensure(big_cap));
 	PGX_TRY(gw.big_count.ensure(8));
-#ifdef PGX_STAGE_PROBES
-	// measurement builds keep round 3's comparison forms of the main-table tier (read once per process)
-	static const bool pools1_env = getenv("PGX_GAP_POOLS1") != nullptr; // the one-pass pools
-	static const bool pools2 = getenv("PGX_GAP_POOLS2") != nullptr;     // round 2's two-pass pools
-	const bool binned = !long_reads && !pools1_env;
-#else
-	constexpr bool pools2 = false;
 	const bool binned = !long_reads;
-#endif
 	if (binned) {
 		PGX_TRY(gw.items.ensure(hit_cap)); // the main table's slots in (region, bin) order
 		PGX_TRY(gw.items1.ensure(hit_cap + 16)); // (read as 16-byte words / 4-byte words of keys)
 		PGX_TRY(gw.keys1.ensure(hit_cap + 16));
 		PGX_TRY(gw.bins.ensure(kBinsWords));
-	}
-	if (pools2) {
-		PGX_TRY(gw.side_main.ensure(hit_cap)); // the left side's result of every HSP, parked between the two passes
-		PGX_TRY(gw.side_ovf.ensure(ovf_cap));
 	}
 	PGX_TRY(gw.order.ensure((size_t)10240 * kBlkItems));
 	// (the list may have been grown by the caller after a step that overflowed it: the later tiers' lists and the parked
@@ -2459,7 +2303,6 @@ int gapped_stage(const DbView &dv, const ReadsView &rv, pgx_hit *main_table, con
 	PGX_HIP(hipMemsetAsync(gw.big_count.data(), 0, 8 * sizeof(uint32_t), stream));
 	const uint32_t n = rv.n;
 	const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)n + 63) / 64, 256ull * 40);
-	const int dbg = 0; // (round 2's truncation probes are gone: a truncated stage leaves seed records where the stages behind expect hits)
 	if (binned) {
 		// the main table's slots by database region, within a region by key byte, costliest first: counting sorts that
 		// stream over one byte (then five) per slot
@@ -2476,82 +2319,49 @@ int gapped_stage(const DbView &dv, const ReadsView &rv, pgx_hit *main_table, con
 	uint32_t *cnt = gw.big_count.data(); // [0] list A, [1] B (both checked by the caller), [2] C (in A's buffer), [3] D (in B's), [4] E (in A's), [5] the first tier's own appends to B
 	// (long reads: every HSP goes straight to the wide kernels, which read list A; reads of 321-512 bases: the first tier
 	// holds 40 differences a side with the full statistics, what it cannot finish goes to list A and the wide kernels too)
-	static const bool no_deep = getenv("PGX_GAP_NODEEP") != nullptr; // (measurement aid, read once per process)
-	const bool deep = !long_reads && max_len > gapped_deep_from() && !no_deep;
+	const bool deep = !long_reads && max_len > kGapDeepFrom;
 	const bool one_list = long_reads || deep;
 	const TierLists tl = { listA, one_list ? listA : listB, cnt, one_list ? cnt : cnt + 1, cap, one_list ? nullptr : cnt + 5 };
 	// staged sequences sized for the batch's longest read (the LDS footprint decides the occupancy).  The lean rows over
 	// the two tables; then the rows with the full statistics over what they listed (list A), which lists for the wider tiers (B)
-#ifdef PGX_STAGE_PROBES
-#define PGX_POOLS2_MAIN(ML, WV)                                                                                                             \
-	hipLaunchKernelGGL((k_gapped_fast<0, ML, WV, kGFastD>), dim3(grid_wv ? grid_wv : 1), dim3(64), 0, stream, v, main_table, hit_cap, read_start, \
-			   read_cnt, n, (const unsigned long long *)nullptr, listA, cnt, cap, gw.side_main.data(), dbg, gw.order.data())
-#define PGX_POOLS2_OVF(ML, WV)                                                                                                              \
-	hipLaunchKernelGGL((k_gapped_fast<1, ML, WV, kGFastD>), dim3(256), dim3(64), 0, stream, v, ovf_table, ovf_cap, (const uint32_t *)nullptr, \
-			   (const uint32_t *)nullptr, 0u, ovf_count, listA, cnt, cap, gw.side_ovf.data(), dbg, gw.order.data())
-#else
-#define PGX_POOLS2_MAIN(ML, WV) ((void)0)
-#define PGX_POOLS2_OVF(ML, WV) ((void)0)
-#endif
-#define PGX_GAPPED_LAUNCH(ML, WV, DD)                                                                                                          \
-	do {                                                                                                                                 \
-		v.key = main_key;                                                                                                            \
-		const unsigned grid_wv = std::min<unsigned>(grid, 256u * 4u * WV * 2u); /* two full rounds of resident wavefronts */  \
-		if (binned)                                                                                                                  \
-			hipLaunchKernelGGL((k_gapped_rows<ML, (WV > 4 ? 4 : WV), DD>), dim3(256u * 4u * (WV > 4 ? 4 : WV) * 2u), dim3(64), 0, stream, v, main_table, \
-					   gw.items.data(), gw.bins.data(), tl);                                                                  \
-		else if (pools2)                                                                                                             \
-			PGX_POOLS2_MAIN(ML, WV);                                                                                                 \
-		else                                                                                                                         \
-			hipLaunchKernelGGL((k_gapped_pool<false, ML, (WV > 4 ? 4 : WV)>), dim3(std::max(1u, std::min<unsigned>(grid, 256u * 4u * (WV > 4 ? 4 : WV) * 2u))), dim3(64), 0, stream, \
-					   v, main_table, hit_cap, read_start, read_cnt, n, (const unsigned long long *)nullptr, tl, gw.order.data()); \
-		v.key = ovf_key;                                                                                                             \
-		if (pools2)                                                                                                                  \
-			PGX_POOLS2_OVF(ML, WV);                                                                                                  \
-		else                                                                                                                         \
-			hipLaunchKernelGGL((k_gapped_pool<true, ML, (WV > 4 ? 4 : WV)>), dim3(256), dim3(64), 0, stream, v, ovf_table, ovf_cap,       \
-					   (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u, ovf_count, tl, gw.order.data()); \
-		if (!one_list)                                                                                                               \
-			hipLaunchKernelGGL((k_gapped_fast<2, ML, WV, kGFastD>), dim3(256 * 4 * WV), dim3(64), 0, stream, v,                      \
-					   reinterpret_cast<pgx_hit *>(listA), (unsigned long long)cap, (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u, \
-					   reinterpret_cast<const unsigned long long *>(cnt), listB, cnt + 1, cap, gw.side_list.data(), 0, gw.order.data()); \
-	} while (0)
+	auto launch_tiers = [&](auto ml, auto wv, auto dd) {
+		constexpr int ML = decltype(ml)::value, WV = decltype(wv)::value, DD = decltype(dd)::value;
+		v.key = main_key;
+		if (binned)
+			hipLaunchKernelGGL((k_gapped_rows<ML, WV, DD>), dim3(256u * 4u * WV * 2u), dim3(64), 0, stream, v, main_table, gw.items.data(), gw.bins.data(), tl);
+		else
+			hipLaunchKernelGGL((k_gapped_pool<false, ML, WV>), dim3(std::max(1u, std::min<unsigned>(grid, 256u * 4u * WV * 2u))), dim3(64), 0, stream, v,
+					   main_table, hit_cap, read_start, read_cnt, n, (const unsigned long long *)nullptr, tl, gw.order.data());
+		v.key = ovf_key;
+		hipLaunchKernelGGL((k_gapped_pool<true, ML, WV>), dim3(256), dim3(64), 0, stream, v, ovf_table, ovf_cap, (const uint32_t *)nullptr,
+				   (const uint32_t *)nullptr, 0u, ovf_count, tl, gw.order.data());
+		if (!one_list)
+			hipLaunchKernelGGL((k_gapped_list<ML, WV, kGFastD>), dim3(256 * 4 * WV), dim3(64), 0, stream, v, reinterpret_cast<pgx_hit *const *>(listA),
+					   (unsigned long long)cap, cnt, listB, cnt + 1, cap, gw.side_list.data(), gw.order.data());
+	};
+	using std::integral_constant;
 	if (max_len <= 160)
-		PGX_GAPPED_LAUNCH(160, PGX_LEAN_WAVES, kGFastD);
+		launch_tiers(integral_constant<int, 160>{}, integral_constant<int, kLeanWaves>{}, integral_constant<int, kGFastD>{});
 	else if (max_len <= 192)
-		PGX_GAPPED_LAUNCH(192, 4, kGFastD);
-	else if (max_len <= 320 && deep)
-		PGX_GAPPED_LAUNCH(320, 2, kGFastD2);
+		launch_tiers(integral_constant<int, 192>{}, integral_constant<int, 4>{}, integral_constant<int, kGFastD>{});
 	else if (max_len <= 320)
-		PGX_GAPPED_LAUNCH(320, 3, kGFastD);
+		launch_tiers(integral_constant<int, 320>{}, integral_constant<int, 3>{}, integral_constant<int, kGFastD>{});
 	else if (deep)
-		PGX_GAPPED_LAUNCH(512, 2, kGFastD2);
+		launch_tiers(integral_constant<int, 512>{}, integral_constant<int, 2>{}, integral_constant<int, kGFastD2>{});
 	else
-		PGX_GAPPED_LAUNCH(512, 2, kGFastD);
-#undef PGX_GAPPED_LAUNCH
-#undef PGX_POOLS2_MAIN
-#undef PGX_POOLS2_OVF
+		launch_tiers(integral_constant<int, 512>{}, integral_constant<int, 2>{}, integral_constant<int, kGFastD>{});
 	// the wider tiers, each passing on what it cannot hold: the lane-per-HSP kernel with rows for 40 differences a side
 	// and the X-drop history (reads of <= 512 bases without ambiguity letters: most of what reads of 300-500 bases
-	// list), then one wavefront per HSP with rows for 62 differences, then for the spec's 1 000
+	// list), then one wavefront per HSP: one lane per diagonal, then rows for 62 differences, then for the spec's 1 000
 	if (!one_list)
-		hipLaunchKernelGGL((k_gapped_fast<2, 512, 2, kGFastD2>), dim3(256 * 6 * 2), dim3(64), 0, stream, v,
-				   reinterpret_cast<pgx_hit *>(listB), (unsigned long long)cap, (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u,
-				   reinterpret_cast<const unsigned long long *>(cnt + 1), listA, cnt + 2, cap,
-				   gw.side_list.data(), 0, gw.order.data());
+		hipLaunchKernelGGL((k_gapped_list<512, 2, kGFastD2>), dim3(256 * 6 * 2), dim3(64), 0, stream, v, reinterpret_cast<pgx_hit *const *>(listB),
+				   (unsigned long long)cap, cnt + 1, listA, cnt + 2, cap, gw.side_list.data(), gw.order.data());
 	// (list C, or list A itself for long reads) -> one lane per diagonal -> D -> the LDS rows for 62 differences -> E -> for 1 000
 	const uint32_t *c_diag = one_list ? cnt : cnt + 2;
-	static const bool no_diag = getenv("PGX_GAP_NODIAG") != nullptr; // (measurement aid: the wide kernels alone, as in round 2)
-	if (no_diag) {
-		hipLaunchKernelGGL(k_gapped_big<62>, dim3(256 * 32), dim3(64), 0, stream, v, (const unsigned long long *)listA, c_diag, cap, listB, cnt + 3);
-		hipLaunchKernelGGL(k_gapped_big<kGDmax>, dim3(256 * 8), dim3(64), 0, stream, v, (const unsigned long long *)listB, cnt + 3, cap,
-				   (unsigned long long *)nullptr, (uint32_t *)nullptr);
-	} else {
-		hipLaunchKernelGGL(k_gapped_diag, dim3(256 * 32), dim3(64), 0, stream, v, (const unsigned long long *)listA, c_diag, cap, listB, cnt + 3);
-		hipLaunchKernelGGL(k_gapped_big<62>, dim3(256 * 32), dim3(64), 0, stream, v, (const unsigned long long *)listB, cnt + 3, cap, listA, cnt + 4);
-		hipLaunchKernelGGL(k_gapped_big<kGDmax>, dim3(256 * 8), dim3(64), 0, stream, v, (const unsigned long long *)listA, cnt + 4, cap,
-				   (unsigned long long *)nullptr, (uint32_t *)nullptr);
-	}
+	hipLaunchKernelGGL(k_gapped_diag, dim3(256 * 32), dim3(64), 0, stream, v, (const unsigned long long *)listA, c_diag, cap, listB, cnt + 3);
+	hipLaunchKernelGGL(k_gapped_big<62>, dim3(256 * 32), dim3(64), 0, stream, v, (const unsigned long long *)listB, cnt + 3, cap, listA, cnt + 4);
+	hipLaunchKernelGGL(k_gapped_big<kGDmax>, dim3(256 * 8), dim3(64), 0, stream, v, (const unsigned long long *)listA, cnt + 4, cap,
+			   (unsigned long long *)nullptr, (uint32_t *)nullptr);
 	PGX_HIP(hipGetLastError());
 	return 0;
 }

@@ -79,7 +79,7 @@ extern "C" int pgx_probe_gather(uint64_t table_bytes, int stream, double *lines_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The issue roof of the gapped stage's instruction mix.  k_gapped_fast is integer VALU (v_max3_i32, adds, compares,
+// The issue roof of the gapped stage's instruction mix.  Its lane-per-HSP kernels are integer VALU (v_max3_i32, adds, compares,
 // v_alignbit, v_ffbl), scalar bookkeeping and LDS reads on letters held per lane.  What a SIMD delivers for each such
 // instruction at 1 .. 8 resident wavefronts is measured here, not assumed: every wavefront runs `iters` trips of 64
 // vector instructions of ONE kind over 8 independent registers (instruction j works on register j mod 8, so a dependent

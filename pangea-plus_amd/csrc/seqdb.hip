@@ -854,8 +854,7 @@ static int reads_finish(pgx_reads *rd)
 		PGX_HIP(hipGetLastError());
 	}
 	PGX_HIP(hipDeviceSynchronize());
-	if (!getenv("PGX_NO_DUST"))
-		PGX_TRY(reads_dust(rd));
+	PGX_TRY(reads_dust(rd));
 	return reads_build_classes(rd); // (after the DUST pass: reads with masked bases are a search class of their own)
 }
 

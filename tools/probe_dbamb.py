@@ -24,14 +24,8 @@ for tag in ("clean", "iupac"):
         open(fa, "w").write("".join(out)); del out
     pg.makeblastdb(fa, os.path.join(tmp, tag))
     db = pg.Db.open(os.path.join(tmp, tag))
-    for sw in ("", "1"):
-        if sw:
-            os.environ["PGX_NO_AMB_BLK"] = sw
-        else:
-            os.environ.pop("PGX_NO_AMB_BLK", None)
-        for it in range(3):
-            h = _capi.blast_search(db, reads); st = _capi.stage_times(); k = len(h); del h
-        print("%s database (has_amb=%d, block bitmap %s): seed %.1f ms sort %.1f ms -> %.1f M reads/s, %d hits" % (
-            tag, db.shape()[2], "off" if sw else "on", st.seed_extend_ms, st.sort_ms, n / st.total_ms / 1e3, k), flush=True)
-    os.environ.pop("PGX_NO_AMB_BLK", None)
+    for it in range(3):
+        h = _capi.blast_search(db, reads); st = _capi.stage_times(); k = len(h); del h
+    print("%s database (has_amb=%d): seed %.1f ms sort %.1f ms -> %.1f M reads/s, %d hits" % (
+        tag, db.shape()[2], st.seed_extend_ms, st.sort_ms, n / st.total_ms / 1e3, k), flush=True)
     del db
