@@ -2,6 +2,7 @@
 """bench.py — classified reads/s of the classify -> lineage -> consensus hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: one rank per GPU via torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (+ the side lines and the roofs that take runs of their own)
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on): synthetic 150-bp reads
 (1 % substitutions, either strand) against the synthetic 1 Gbp 16S-like database (666 667 x 1 500 bp,
@@ -16,9 +17,15 @@ rank 0 and broadcast ONCE over RCCL before the timed region.
 Prints one JSON line (rank 0).  `roofline` is for the longest stage of the step (spec v2: the gapped stage,
 k_gapped_rows and its sorting passes, or the seed stage -- they are within a per cent of each other; the other
 one's object rides along as `roofline.seed_extend` / `roofline.gapped`): algorithmic bytes per launch
- / its HIP-event duration, against 8 TB/s, with the two roofs that really bound it
-measured in the same run (random 64-byte lines per second, vector instructions per second per SIMD).
-`cpu_baseline` is the oracle's CPU restatement of the same chain ("port") on a bounded sample, rank 0, N = 1 only.
+ / its HIP-event duration, against 8 TB/s.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.
+--full adds what takes runs of its own, after the timed steps: `dust_at_import_only` (the K steps again with the
+DUST bits of the batch import reused), the two roofs that really bound the stages measured in the same run
+(`roofline.*.random_line_roof`: random 64-byte lines per second; `roofline.*.issue`: vector instructions per second
+per SIMD; null in a plain run), and at N = 1 the file-to-file line `inclusive` and `cpu_baseline`, the oracle's CPU
+restatement of the same chain ("port") on a bounded sample (both skipped by --no-cpu-baseline; `cpu_baseline` is
+null otherwise).
 """
 import argparse
 import ctypes as C
@@ -192,9 +199,12 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reads", type=int, default=10_000_000, help="reads per GPU per step")
-    ap.add_argument("--cpu-sample", type=int, default=200000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--inclusive-sample", type=int, default=2_000_000, help="reads of the file-to-file line (0: skip it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the DUST-at-import side line, the random-line and issue roofs and "
+                         "(N = 1) the file-to-file line and the CPU baseline; a plain run prints the headline figures alone")
+    ap.add_argument("--cpu-sample", type=int, default=200000, help="reads of the CPU baseline (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the file-to-file line and the CPU baseline")
+    ap.add_argument("--inclusive-sample", type=int, default=2_000_000, help="reads of the file-to-file line (--full; 0: skip it)")
     ap.add_argument("--n-seq", type=int, default=666667)
     ap.add_argument("--ungapped", action="store_true", help="blastn -ungapped: stop after the ungapped stage (spec v1, round 1's tables)")
     ap.add_argument("--dry-ranks", action="store_true",
@@ -388,19 +398,21 @@ def main():
             if rank == 0:
                 dump_outputs(args.dump_outputs, kept["hits"], kept["recs"], kept["first"])
             kept.clear()  # (the hit table of a full batch is several GB of HBM)
-        # the same K steps with the DUST bits of the batch import reused (the search then skips its first stage): a side line
-        fence()
-        db.set_dust_each_search(False)
-        t0 = time.perf_counter()
-        for i in range(args.warmup, args.warmup + args.steps):
-            step(i)
-        fence()
-        dt_nodust = time.perf_counter() - t0
-        db.set_dust_each_search(True)
-        if world > 1:
-            tt = torch.tensor([dt_nodust], dtype=torch.float64, device=dev)
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt_nodust = float(tt.item())
+        dt_nodust = None
+        if args.full:
+            # the same K steps with the DUST bits of the batch import reused (the search then skips its first stage): a side line
+            fence()
+            db.set_dust_each_search(False)
+            t0 = time.perf_counter()
+            for i in range(args.warmup, args.warmup + args.steps):
+                step(i)
+            fence()
+            dt_nodust = time.perf_counter() - t0
+            db.set_dust_each_search(True)
+            if world > 1:
+                tt = torch.tensor([dt_nodust], dtype=torch.float64, device=dev)
+                dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+                dt_nodust = float(tt.item())
 
         if rank == 0:
             last = stages[-1]
@@ -417,19 +429,20 @@ def main():
                     traffic = gap_traffic = None
             # the roof of the kernel's access shape, measured here and now: 64-byte lines per second for random 8-byte
             # lane loads over a 16 GiB table (pgx_probe_gather), against the kernel's L2 requests per second (requests
-            # per read from the PMC passes of profiles/, x reads, / measured kernel time)
+            # per read from the PMC passes of profiles/, x reads, / measured kernel time); --full only
             line_roof = None
-            try:
-                lps, pms = C.c_double(), C.c_double()
-                _capi._check(pg.lib().pgx_probe_gather(16 << 30, 0, C.byref(lps), C.byref(pms)))
-                per_read = json.load(open(tp)).get("k_seed_extend_l2_requests_per_read")
-                if per_read and lps.value > 0:
-                    req = per_read * B * args.steps / (kernel_ms * 1e-3)
-                    line_roof = {"roof_lines_per_s": lps.value, "roof_as_GBps_of_64B_lines": lps.value * 64 / 1e9,
-                                 "kernel_l2_requests_per_s": req, "frac": req / lps.value,
-                                 "basis": "random 8-byte lane loads, 16 GiB table, 8 loads in flight per lane; kernel requests = %.1f per read (TCC_HIT+TCC_MISS, profiles/traffic.json)" % per_read}
-            except Exception as e:  # an older library without the probe: the line is still printed
-                line_roof = {"error": str(e)}
+            if args.full:
+                try:
+                    lps, pms = C.c_double(), C.c_double()
+                    _capi._check(pg.lib().pgx_probe_gather(16 << 30, 0, C.byref(lps), C.byref(pms)))
+                    per_read = json.load(open(tp)).get("k_seed_extend_l2_requests_per_read")
+                    if per_read and lps.value > 0:
+                        req = per_read * B * args.steps / (kernel_ms * 1e-3)
+                        line_roof = {"roof_lines_per_s": lps.value, "roof_as_GBps_of_64B_lines": lps.value * 64 / 1e9,
+                                     "kernel_l2_requests_per_s": req, "frac": req / lps.value,
+                                     "basis": "random 8-byte lane loads, 16 GiB table, 8 loads in flight per lane; kernel requests = %.1f per read (TCC_HIT+TCC_MISS, profiles/traffic.json)" % per_read}
+                except Exception as e:  # an older library without the probe: the line is still printed
+                    line_roof = {"error": str(e)}
             out = {
                 "metric": "classified reads/sec (+ HBM GB/s fraction), 150 bp vs 1 Gbp db, 1/2/4/8 GPU",
                 "value": world * B * args.steps / dt, "unit": "reads/s", "n_gpus": world, "steps": args.steps,
@@ -441,8 +454,9 @@ def main():
                            "reads_per_gpu_per_step": B, "db_bases": int(cfg.n_seq) * int(cfg.seq_len), "db_seqs": int(cfg.n_seq),
                            "read_len": int(cfg.read_len), "parallelism": "read-sharded x%d, index broadcast once over RCCL" % world,
                            "spec": "pgx-blastn v1 (-ungapped)" if args.ungapped else "pgx-blastn v2 (gapped)"},
-                "dust_at_import_only": {"value": world * B * args.steps / dt_nodust, "unit": "reads/s", "ms_per_step": 1e3 * dt_nodust / args.steps,
-                                        "note": "side line: the same steps reusing the DUST bits made when the batch was imported (pgx_db_set_dust_each_search(0)); `value` computes them inside every step"},
+                "dust_at_import_only": None if dt_nodust is None else {
+                    "value": world * B * args.steps / dt_nodust, "unit": "reads/s", "ms_per_step": 1e3 * dt_nodust / args.steps,
+                    "note": "side line: the same steps reusing the DUST bits made when the batch was imported (pgx_db_set_dust_each_search(0)); `value` computes them inside every step"},
                 "roofline": None,
                 "stages_ms_last_step": {"dust": last.dust_ms, "seed_extend": last.seed_extend_ms, "gapped": last.gapped_ms, "gapped_listed_hsps": last.gapped_wide,
                                         "group": last.group_ms,
@@ -484,23 +498,24 @@ def main():
                 except Exception:
                     lines_roof = None
                 issue = None
-                try:
-                    fast, slow = (C.c_double * 4)(), (C.c_double * 4)()
-                    _capi._check(pg.lib().pgx_probe_issue(4, 0, fast))   # v_add_u32: the two-operand kind
-                    _capi._check(pg.lib().pgx_probe_issue(4, 1, slow))   # v_max3_i32: every other kind
-                    valu_per_read = tj.get("k_gapped_rows_valu_instructions_per_read")
-                    issue = {"roof_fast_kind_per_s_per_simd": fast[0], "roof_other_kinds_per_s_per_simd": slow[0]}
-                    if valu_per_read and full:
-                        per_s_per_simd = valu_per_read * B * args.steps / (tj.get("k_gapped_rows_share_of_stage", 1.0) * gap_ms * 1e-3) / 1024
-                        issue.update({"valu_instructions_per_read": valu_per_read, "kernel_valu_per_s_per_simd": per_s_per_simd,
-                                      "busy_if_all_fast": per_s_per_simd / fast[0], "busy_if_all_other": per_s_per_simd / slow[0],
-                                      "basis": "SQ_INSTS_VALU of k_gapped_rows per read (profiles/) x reads / (1024 SIMDs x kernel time), against the measured issue rates of the two kinds of vector instruction at 4 wavefronts per SIMD"})
-                except Exception as e:
-                    issue = {"error": str(e)}
+                if args.full:
+                    try:
+                        fast, slow = (C.c_double * 4)(), (C.c_double * 4)()
+                        _capi._check(pg.lib().pgx_probe_issue(4, 0, fast))   # v_add_u32: the two-operand kind
+                        _capi._check(pg.lib().pgx_probe_issue(4, 1, slow))   # v_max3_i32: every other kind
+                        valu_per_read = tj.get("k_gapped_rows_valu_instructions_per_read")
+                        issue = {"roof_fast_kind_per_s_per_simd": fast[0], "roof_other_kinds_per_s_per_simd": slow[0]}
+                        if valu_per_read and full:
+                            per_s_per_simd = valu_per_read * B * args.steps / (tj.get("k_gapped_rows_share_of_stage", 1.0) * gap_ms * 1e-3) / 1024
+                            issue.update({"valu_instructions_per_read": valu_per_read, "kernel_valu_per_s_per_simd": per_s_per_simd,
+                                          "busy_if_all_fast": per_s_per_simd / fast[0], "busy_if_all_other": per_s_per_simd / slow[0],
+                                          "basis": "SQ_INSTS_VALU of k_gapped_rows per read (profiles/) x reads / (1024 SIMDs x kernel time), against the measured issue rates of the two kinds of vector instruction at 4 wavefronts per SIMD"})
+                    except Exception as e:
+                        issue = {"error": str(e)}
                 gap_roof = {"bound": "hbm", "kernel": "k_gapped_rows (+ k_reg_* / k_seg_* sorting passes, list tiers)", "achieved": g_ach,
                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": g_ach / HBM_PEAK_GBS, "traffic": gap_traffic,
                             "alg_bytes_per_launch": gap_bytes / args.steps, "kernel_ms_per_launch": gap_ms / args.steps,
-                            "note": "the stage's real roofs are the random-line rate and the issue rate, both measured here: see DESIGN.md sections 6-7",
+                            "note": "the stage's real roofs are the random-line rate and the issue rate, both measured in the same run by --full: see DESIGN.md sections 6-7",
                             "random_line_roof": lines_roof, "issue": issue}
                 # the longer of the two stages is the line's `roofline`, the other one rides along (since the end of round 3
                 # they are within a per cent of each other and change places from run to run)
@@ -510,7 +525,7 @@ def main():
                     out["roofline"] = dict(seed_roof, gapped=gap_roof)
             else:
                 out["roofline"] = seed_roof  # (-ungapped: spec v1 has no gapped stage)
-            if world == 1 and args.inclusive_sample > 0 and not args.no_cpu_baseline:
+            if args.full and world == 1 and args.inclusive_sample > 0 and not args.no_cpu_baseline:
                 try:
                     # two passes over the same files, the second is the line (as `cpu_baseline` is a best of two): the first one
                     # also pins the process's copy buffers and builds the handle's formatter tables, which a job pays once,
@@ -520,7 +535,7 @@ def main():
                     out["inclusive"]["first_pass"] = {"value": cold["value"], "stages_s": cold["stages_s"]}
                 except Exception as e:  # the line is still printed
                     out["inclusive"] = {"error": str(e)}
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(cfg, tmp, args.cpu_sample)
             else:
                 out["cpu_baseline"] = None
