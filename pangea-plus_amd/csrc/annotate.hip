@@ -311,143 +311,135 @@ extern "C" {
 int pgx_taxcollect_file(pgx_taxdb *db, const char *in_path, const char *out_path, char **report_text)
 {
 	Text report;
-	auto done = [&](int rc) {
-		if (report_text)
-			*report_text = report.release_malloc(nullptr);
-		return rc;
-	};
-	if (!db || !in_path || !out_path)
-		return done(fail(PGX_E_ARG, "taxcollector: -f and -o are required"));
-	int rc = require_device();
-	if (rc < 0)
-		return done(rc);
-	bool ok;
-	std::string text = read_text_file(in_path, &ok);
-	if (!ok) {
-		report.printf("Error: Unable to open classification results file %s.\n", in_path); // taxcollector:31-34
-		return done(fail(PGX_E_IO, "cannot open %s", in_path));
-	}
-	// pass 1 (host): lines up to the first empty one (taxcollector:83-87) and where their gi texts are; nothing is copied
-	struct LineRef {
-		size_t s, n, g, gn; // line start/length, gi text start/length
-	};
-	std::vector<LineRef> lines;
-	std::vector<int32_t> gi_num;
-	int hang_line = -1;
-	for (size_t s = 0; s < text.size();) {
-		const char *nl = (const char *)memchr(text.data() + s, '\n', text.size() - s);
-		const size_t e = nl ? (size_t)(nl - text.data()) : text.size();
-		const char *line = text.data() + s;
-		const size_t n = e - s;
-		bool only_bars = true;
-		for (size_t k = 0; k < n && only_bars; k++)
-			only_bars = line[k] == '|';
-		if (only_bars)
-			break;
-		const char *b1 = (const char *)memchr(line, '|', n);
-		size_t g = 0, gn = 0;
-		if (b1) {
-			g = (size_t)(b1 - line) + 1;
-			const char *b2 = (const char *)memchr(line + g, '|', n - g);
-			gn = b2 ? (size_t)(b2 - line) - g : n - g;
+	return with_text(report, report_text, [&]() -> int {
+		if (!db || !in_path || !out_path)
+			return fail(PGX_E_ARG, "taxcollector: -f and -o are required");
+		PGX_TRY(require_device());
+		bool ok;
+		std::string text = read_text_file(in_path, &ok);
+		if (!ok) {
+			report.printf("Error: Unable to open classification results file %s.\n", in_path); // taxcollector:31-34
+			return fail(PGX_E_IO, "cannot open %s", in_path);
 		}
-		if (!b1 || gn == 0) {
-			hang_line = (int)lines.size();
-			break; // `./tax_class -s` without an id: the reference recurses forever
-		}
-		lines.push_back({ s, n, s + g, gn });
-		gi_num.push_back(atoi(std::string(line + g, gn).c_str()));
-		s = e + 1;
-	}
-	// pass 2 (device): one walk per line
-	const size_t n = lines.size();
-	std::vector<int32_t> lin(n * PGX_LINEAGE_SLOTS), cnt(n), st(n), leaf(n);
-	if (n) {
-		DevBuf<int32_t> d_gi, d_lin, d_cnt, d_st, d_leaf;
-		rc = d_gi.alloc(n);
-		if (rc == 0) rc = d_lin.alloc(n * PGX_LINEAGE_SLOTS, 0, 0, true);
-		if (rc == 0) rc = d_cnt.alloc(n);
-		if (rc == 0) rc = d_st.alloc(n);
-		if (rc == 0) rc = d_leaf.alloc(n);
-		if (rc == 0) rc = d_gi.upload(gi_num.data(), n);
-		if (rc == 0) rc = tax_walk_device(db, d_gi.data(), (int64_t)n, d_lin.data(), d_cnt.data(), d_st.data(), d_leaf.data());
-		if (rc == 0) rc = d_lin.download(lin.data(), lin.size());
-		if (rc == 0) rc = d_cnt.download(cnt.data(), n);
-		if (rc == 0) rc = d_st.download(st.data(), n);
-		if (rc == 0) rc = d_leaf.download(leaf.data(), n);
-		if (rc < 0)
-			return done(rc);
-	}
-	// the driver stops at the first line whose walk never ends (or is too long for this build)
-	size_t stop_at = n;
-	int status = 0;
-	for (size_t i = 0; i < n; i++)
-		if (st[i] == 2 || st[i] == 3) {
-			stop_at = i;
-			const std::string g(text, lines[i].g, lines[i].gn);
-			status = st[i] == 2 ? fail(PGX_E_REFHANG, "line %zu (GI %s): the reference driver never terminates on this taxonomy walk", i + 1, g.c_str())
-					    : fail(PGX_E_LIMIT, "line %zu: lineage longer than %d elements", i + 1, PGX_LINEAGE_SLOTS);
-			break;
-		}
-	// pass 3 (host, all cores): text.  Lines are independent; every worker renders a contiguous block with its own
-	// name cache and remembers the lineage text per gi, the blocks are joined in order.
-	const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-	const unsigned workers = (unsigned)std::max<size_t>(1, std::min<size_t>(hw, stop_at / 20000 + 1));
-	std::vector<std::string> outs(workers), reps(workers);
-	auto work = [&](unsigned w) {
-		const size_t i0 = stop_at * w / workers, i1 = stop_at * (w + 1) / workers;
-		LineageRenderer ren(db);
-		std::unordered_map<std::string, std::string> memo;
-		std::string &o = outs[w], &r = reps[w];
-		o.reserve((i1 - i0) * 160);
-		r.reserve((i1 - i0) * 64);
-		char buf[96];
-		for (size_t i = i0; i < i1; i++) {
-			const std::string g(text, lines[i].g, lines[i].gn);
-			if (st[i] == 1) {
-				r += "Searching upper node for TAXID 0\n.\n"; // taxcollector:176 with "0\n"
-				r += "\n\nTAXID zero GI = " + g + ".\n\n";
-			} else {
-				const int k = snprintf(buf, sizeof buf, "Searching upper node for TAXID %d.\nDone for TAXID %d.\n", leaf[i], leaf[i]);
-				r.append(buf, (size_t)k);
+		// pass 1 (host): lines up to the first empty one (taxcollector:83-87) and where their gi texts are; nothing is copied
+		struct LineRef {
+			size_t s, n, g, gn; // line start/length, gi text start/length
+		};
+		std::vector<LineRef> lines;
+		std::vector<int32_t> gi_num;
+		int hang_line = -1;
+		for (size_t s = 0; s < text.size();) {
+			const char *nl = (const char *)memchr(text.data() + s, '\n', text.size() - s);
+			const size_t e = nl ? (size_t)(nl - text.data()) : text.size();
+			const char *line = text.data() + s;
+			const size_t n = e - s;
+			bool only_bars = true;
+			for (size_t k = 0; k < n && only_bars; k++)
+				only_bars = line[k] == '|';
+			if (only_bars)
+				break;
+			const char *b1 = (const char *)memchr(line, '|', n);
+			size_t g = 0, gn = 0;
+			if (b1) {
+				g = (size_t)(b1 - line) + 1;
+				const char *b2 = (const char *)memchr(line + g, '|', n - g);
+				gn = b2 ? (size_t)(b2 - line) - g : n - g;
 			}
-			auto it = memo.find(g);
-			if (it == memo.end())
-				it = memo.emplace(g, ren.render(&lin[i * PGX_LINEAGE_SLOTS], cnt[i], st[i], g)).first;
-			emit_collected_fast(text.data() + lines[i].s, lines[i].n, it->second, o);
+			if (!b1 || gn == 0) {
+				hang_line = (int)lines.size();
+				break; // `./tax_class -s` without an id: the reference recurses forever
+			}
+			lines.push_back({ s, n, s + g, gn });
+			gi_num.push_back(atoi(std::string(line + g, gn).c_str()));
+			s = e + 1;
 		}
-	};
-	if (workers == 1) {
-		work(0);
-	} else {
-		std::vector<std::thread> th;
-		for (unsigned w = 0; w < workers; w++)
-			th.emplace_back(work, w);
-		for (auto &t : th)
-			t.join();
-	}
-	std::string out;
-	size_t total_out = 0, total_rep = 0;
-	for (unsigned w = 0; w < workers; w++) {
-		total_out += outs[w].size();
-		total_rep += reps[w].size();
-	}
-	out.reserve(total_out);
-	report.s.reserve(report.s.size() + total_rep);
-	for (unsigned w = 0; w < workers; w++) {
-		out += outs[w];
-		report.s += reps[w];
-		std::string().swap(outs[w]);
-		std::string().swap(reps[w]);
-	}
-	if (status == 0 && hang_line >= 0)
-		status = fail(PGX_E_REFHANG, "line %d has no gi|N| subject id: the reference driver never terminates on it", hang_line + 1);
-	int wrc = write_text_file(out_path, out);
-	if (wrc < 0) {
-		report.printf("Error: Unable to open output file %s.\n", out_path);
-		return done(wrc);
-	}
-	return done(status);
+		// pass 2 (device): one walk per line
+		const size_t n = lines.size();
+		std::vector<int32_t> lin(n * PGX_LINEAGE_SLOTS), cnt(n), st(n), leaf(n);
+		if (n) {
+			DevBuf<int32_t> d_gi, d_lin, d_cnt, d_st, d_leaf;
+			PGX_TRY(d_gi.assign(gi_num));
+			PGX_TRY(d_lin.alloc(n * PGX_LINEAGE_SLOTS, 0, 0, true));
+			PGX_TRY(d_cnt.alloc(n));
+			PGX_TRY(d_st.alloc(n));
+			PGX_TRY(d_leaf.alloc(n));
+			PGX_TRY(tax_walk_device(db, d_gi.data(), (int64_t)n, d_lin.data(), d_cnt.data(), d_st.data(), d_leaf.data()));
+			PGX_TRY(d_lin.download(lin.data(), lin.size()));
+			PGX_TRY(d_cnt.download(cnt.data(), n));
+			PGX_TRY(d_st.download(st.data(), n));
+			PGX_TRY(d_leaf.download(leaf.data(), n));
+		}
+		// the driver stops at the first line whose walk never ends (or is too long for this build)
+		size_t stop_at = n;
+		int status = 0;
+		for (size_t i = 0; i < n; i++)
+			if (st[i] == 2 || st[i] == 3) {
+				stop_at = i;
+				const std::string g(text, lines[i].g, lines[i].gn);
+				status = st[i] == 2 ? fail(PGX_E_REFHANG, "line %zu (GI %s): the reference driver never terminates on this taxonomy walk", i + 1, g.c_str())
+						    : fail(PGX_E_LIMIT, "line %zu: lineage longer than %d elements", i + 1, PGX_LINEAGE_SLOTS);
+				break;
+			}
+		// pass 3 (host, all cores): text.  Lines are independent; every worker renders a contiguous block with its own
+		// name cache and remembers the lineage text per gi, the blocks are joined in order.
+		const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+		const unsigned workers = (unsigned)std::max<size_t>(1, std::min<size_t>(hw, stop_at / 20000 + 1));
+		std::vector<std::string> outs(workers), reps(workers);
+		auto work = [&](unsigned w) {
+			const size_t i0 = stop_at * w / workers, i1 = stop_at * (w + 1) / workers;
+			LineageRenderer ren(db);
+			std::unordered_map<std::string, std::string> memo;
+			std::string &o = outs[w], &r = reps[w];
+			o.reserve((i1 - i0) * 160);
+			r.reserve((i1 - i0) * 64);
+			char buf[96];
+			for (size_t i = i0; i < i1; i++) {
+				const std::string g(text, lines[i].g, lines[i].gn);
+				if (st[i] == 1) {
+					r += "Searching upper node for TAXID 0\n.\n"; // taxcollector:176 with "0\n"
+					r += "\n\nTAXID zero GI = " + g + ".\n\n";
+				} else {
+					const int k = snprintf(buf, sizeof buf, "Searching upper node for TAXID %d.\nDone for TAXID %d.\n", leaf[i], leaf[i]);
+					r.append(buf, (size_t)k);
+				}
+				auto it = memo.find(g);
+				if (it == memo.end())
+					it = memo.emplace(g, ren.render(&lin[i * PGX_LINEAGE_SLOTS], cnt[i], st[i], g)).first;
+				emit_collected_fast(text.data() + lines[i].s, lines[i].n, it->second, o);
+			}
+		};
+		if (workers == 1) {
+			work(0);
+		} else {
+			std::vector<std::thread> th;
+			for (unsigned w = 0; w < workers; w++)
+				th.emplace_back(work, w);
+			for (auto &t : th)
+				t.join();
+		}
+		std::string out;
+		size_t total_out = 0, total_rep = 0;
+		for (unsigned w = 0; w < workers; w++) {
+			total_out += outs[w].size();
+			total_rep += reps[w].size();
+		}
+		out.reserve(total_out);
+		report.s.reserve(report.s.size() + total_rep);
+		for (unsigned w = 0; w < workers; w++) {
+			out += outs[w];
+			report.s += reps[w];
+			std::string().swap(outs[w]);
+			std::string().swap(reps[w]);
+		}
+		if (status == 0 && hang_line >= 0)
+			status = fail(PGX_E_REFHANG, "line %d has no gi|N| subject id: the reference driver never terminates on it", hang_line + 1);
+		int wrc = write_text_file(out_path, out);
+		if (wrc < 0) {
+			report.printf("Error: Unable to open output file %s.\n", out_path);
+			return wrc;
+		}
+		return status;
+	});
 }
 
 int pgx_db_bind_taxonomy(pgx_db *db, pgx_taxdb *tax)
@@ -746,23 +738,19 @@ int pgx_rdp_from_file(const char *path, const pgx_reads *reads, const pgx_db *cd
 	const size_t n_trip = ht.n_trip;
 	std::unique_ptr<uint32_t[]> &name_a = ht.name_a, &code_a = ht.code_a;
 	std::unique_ptr<int8_t[]> &rank_a = ht.rank_a;
-	pgx_rdp *rd = new pgx_rdp();
+	std::unique_ptr<pgx_rdp> rd(new pgx_rdp());
 	rd->n = (int64_t)n;
 	rd->max_trip = 0;
 	for (size_t r = 0; r < n; r++) {
 		off[r + 1] = off[r] + trips[r];
 		rd->max_trip = std::max(rd->max_trip, (int)std::min<uint32_t>(trips[r], 8));
 	}
-	int rc = rd->d_off.alloc(n + 1);
-	if (rc == 0) rc = rd->d_off.upload(off.data(), n + 1);
-	if (rc == 0) rc = rd->d_name.alloc(n_trip ? n_trip : 1);
-	if (rc == 0) rc = rd->d_name.upload(name_a.get(), n_trip);
-	if (rc == 0) rc = rd->d_rank.alloc(n_trip ? n_trip : 1);
-	if (rc == 0) rc = rd->d_rank.upload(rank_a.get(), n_trip);
-	if (rc == 0) rc = rd->d_code.alloc(n_trip ? n_trip : 1);
-	if (rc == 0) rc = rd->d_code.upload(code_a.get(), n_trip);
-	if (rc == 0) rc = rd->d_present.alloc(present.size());
-	if (rc == 0) rc = rd->d_present.upload(present.data(), present.size());
+	PGX_TRY(rd->d_off.assign(off));
+	PGX_TRY(rd->d_name.assign(name_a.get(), n_trip));
+	PGX_TRY(rd->d_rank.assign(rank_a.get(), n_trip));
+	PGX_TRY(rd->d_code.assign(code_a.get(), n_trip));
+	PGX_TRY(rd->d_present.alloc(present.size()));
+	PGX_TRY(rd->d_present.upload(present.data(), present.size()));
 	lap("offsets, uploads");
 	// ~300 MB of work arrays and the file's mapping: unmapping them took 0.02 s of this call's 0.115 s; a thread of its own
 	// does it while the caller goes on
@@ -793,11 +781,7 @@ int pgx_rdp_from_file(const char *path, const pgx_reads *reads, const pgx_db *cd
 	}
 	if (trace)
 		fprintf(stderr, "[pgx trace] rdp_from_file in all: %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enter).count());
-	if (rc < 0) {
-		delete rd;
-		return rc;
-	}
-	*out = rd;
+	*out = rd.release();
 	return 0;
 }
 
@@ -1010,38 +994,31 @@ int pgx_rdp_from_synth(const pgx_synth_cfg *cfg, int64_t first, int64_t count, c
 	if ((size_t)(base[6] + cnt[6]) > db->d_node_name_tok.n)
 		return fail(PGX_E_ARG, "bound taxonomy is smaller than the synthetic one");
 	DevBuf<int64_t> d_cnt, d_base;
-	PGX_TRY(d_cnt.alloc(7));
-	PGX_TRY(d_base.alloc(7));
-	PGX_TRY(d_cnt.upload(cnt, 7));
-	PGX_TRY(d_base.upload(base, 7));
-	pgx_rdp *rd = new pgx_rdp();
+	PGX_TRY(d_cnt.assign(cnt, 7));
+	PGX_TRY(d_base.assign(base, 7));
+	std::unique_ptr<pgx_rdp> rd(new pgx_rdp());
 	rd->n = count;
 	rd->max_trip = 6; // the synthetic stream names six ranks per read
 	std::vector<uint32_t> off((size_t)count + 1);
 	for (int64_t i = 0; i <= count; i++)
 		off[(size_t)i] = (uint32_t)(6 * i);
-	int rc = rd->d_off.alloc((size_t)count + 1);
-	if (rc == 0) rc = rd->d_off.upload(off.data(), off.size());
-	if (rc == 0) rc = rd->d_name.alloc((size_t)count * 6 + 1);
-	if (rc == 0) rc = rd->d_rank.alloc((size_t)count * 6 + 1);
-	if (rc == 0) rc = rd->d_code.alloc((size_t)count * 6 + 1);
-	if (rc == 0) rc = rd->d_present.alloc((size_t)count + 1);
-	if (rc == 0 && hipMemset(rd->d_present.data(), 1, (size_t)count + 1) != hipSuccess)
-		rc = fail(PGX_E_NODEVICE, "hipMemset failed");
-	if (rc == 0 && count > 0) {
+	PGX_TRY(rd->d_off.assign(off));
+	PGX_TRY(rd->d_name.alloc((size_t)count * 6 + 1));
+	PGX_TRY(rd->d_rank.alloc((size_t)count * 6 + 1));
+	PGX_TRY(rd->d_code.alloc((size_t)count * 6 + 1));
+	PGX_TRY(rd->d_present.alloc((size_t)count + 1));
+	if (hipMemset(rd->d_present.data(), 1, (size_t)count + 1) != hipSuccess)
+		return fail(PGX_E_NODEVICE, "hipMemset failed");
+	if (count > 0) {
 		hipLaunchKernelGGL(k_synth_rdp, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, cfg->read_seed,
 				   (uint64_t)cfg->n_seq, (uint32_t)cfg->seq_len, (uint32_t)cfg->read_len, (uint64_t)first,
 				   (uint64_t)count, d_cnt.data(), d_base.data(), db->d_node_name_tok.data(), rd->d_name.data(),
 				   rd->d_rank.data(), rd->d_code.data());
 		if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-			rc = fail(PGX_E_NODEVICE, "k_synth_rdp failed");
-	}
-	if (rc < 0) {
-		delete rd;
-		return rc;
+			return fail(PGX_E_NODEVICE, "k_synth_rdp failed");
 	}
 	index_check(db, "rdp_from_synth");
-	*out = rd;
+	*out = rd.release();
 	return 0;
 }
 
@@ -1175,7 +1152,7 @@ int pgx_consensus_format_file(const pgx_db *db, const pgx_reads *reads, const pg
 		char *text = nullptr;
 		size_t len = 0;
 		rc = pgx_consensus_format(db, reads, hits, recs, n, &text, &len);
-		if (rc == 0) {
+		if (rc >= 0) {
 			io_ok = fwrite(text, 1, len, f) == len;
 			total = len;
 		}
@@ -1214,339 +1191,322 @@ int pgx_consensus_batch(const pgx_db *db, const pgx_hits *hits, const pgx_rdp *r
 int pgx_consensus_file(const char *b, const char *r, const char *s_or_null, const char *o, char **log_text)
 {
 	Text log;
-	auto done = [&](int rc) {
-		if (log_text)
-			*log_text = log.release_malloc(nullptr);
-		return rc;
-	};
-	if (!b || !r || !o)
-		return done(fail(PGX_E_ARG, "consensus: -b, -r and -o are required"));
-	int rc = require_device();
-	if (rc < 0)
-		return done(rc);
-	log.s += "\nLoading input files...\n"; // Consensus:19
-	const bool trace = getenv("PGX_TRACE") != nullptr;
-	auto t_now = [] { return std::chrono::steady_clock::now(); };
-	auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-		return std::chrono::duration<double, std::milli>(b - a).count();
-	};
-	const auto t0 = t_now();
-	bool ok;
-	std::string bt = read_text_file(b, &ok);
-	if (!ok) {
-		log.printf("Error: Unable to open %s file.\n", b);
-		return done(fail(PGX_E_IO, "cannot open %s", b));
-	}
-	std::string rt = read_text_file(r, &ok);
-	if (!ok) {
-		log.printf("Error: Unable to open %s file.\n", r);
-		return done(fail(PGX_E_IO, "cannot open %s", r));
-	}
-	if (s_or_null && *s_or_null) {
-		FILE *f = fopen(s_or_null, "r"); // opened and never read (Consensus:40-46)
-		if (!f) {
-			log.printf("Error: Unable to open %s file.\n", s_or_null);
-			return done(fail(PGX_E_IO, "cannot open %s", s_or_null));
+	return with_text(log, log_text, [&]() -> int {
+		if (!b || !r || !o)
+			return fail(PGX_E_ARG, "consensus: -b, -r and -o are required");
+		PGX_TRY(require_device());
+		log.s += "\nLoading input files...\n"; // Consensus:19
+		const bool trace = getenv("PGX_TRACE") != nullptr;
+		auto t_now = [] { return std::chrono::steady_clock::now(); };
+		auto t_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+			return std::chrono::duration<double, std::milli>(b - a).count();
+		};
+		const auto t0 = t_now();
+		bool ok;
+		std::string bt = read_text_file(b, &ok);
+		if (!ok) {
+			log.printf("Error: Unable to open %s file.\n", b);
+			return fail(PGX_E_IO, "cannot open %s", b);
 		}
-		fclose(f);
-	}
-	log.printf("%s\n", o); // Consensus:51
+		std::string rt = read_text_file(r, &ok);
+		if (!ok) {
+			log.printf("Error: Unable to open %s file.\n", r);
+			return fail(PGX_E_IO, "cannot open %s", r);
+		}
+		if (s_or_null && *s_or_null) {
+			FILE *f = fopen(s_or_null, "r"); // opened and never read (Consensus:40-46)
+			if (!f) {
+				log.printf("Error: Unable to open %s file.\n", s_or_null);
+				return fail(PGX_E_IO, "cannot open %s", s_or_null);
+			}
+			fclose(f);
+		}
+		log.printf("%s\n", o); // Consensus:51
 
-	const auto t1 = t_now();
-	// ---- BLAST(+lineage) table: id, lineage tokens, similarity text per line (Consensus:110-122)
-	std::unordered_map<std::string, uint32_t> tmap;
-	std::vector<std::string> ttext;
-	intern_into(tmap, ttext, "");
-	// Nothing is copied per line: lines and their id are spans of the file text.  Pass A (all host cores, contiguous
-	// pieces of the file): line boundaries, the first three columns of split(/\t\t|\t/) and a 64-bit hash of the
-	// lineage and similarity texts.  Pass B (one thread): the lineage column is tokenised once per DISTINCT text (a
-	// hit table names a few hundred thousand lineages millions of times) and the similarity column ranked once per
-	// distinct text; equal hashes are confirmed by comparing the texts.
-	struct Span {
-		size_t s, n;
-	};
-	struct LineInfo {
-		size_t s;
-		uint32_t n, id_n, lin_s, lin_n, sim_s, sim_n; // column offsets are relative to the line start
-		uint64_t lin_h, sim_h;
-	};
-	auto fnv64 = [](const char *p, size_t n) {
-		uint64_t h = 1469598103934665603ull;
-		for (size_t i = 0; i < n; i++)
-			h = (h ^ (unsigned char)p[i]) * 1099511628211ull;
-		return h;
-	};
-	const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-	const unsigned workers = (unsigned)std::max<size_t>(1, std::min<size_t>(hw, bt.size() / (4u << 20) + 1));
-	std::vector<std::vector<LineInfo>> part(workers);
-	{
-		// piece w = [cut[w], cut[w+1]) where every cut is a line start
-		std::vector<size_t> cut(workers + 1, bt.size());
-		cut[0] = 0;
-		for (unsigned w = 1; w < workers; w++) {
-			size_t c = bt.size() * w / workers;
-			const char *nl = c < bt.size() ? (const char *)memchr(bt.data() + c, '\n', bt.size() - c) : nullptr;
-			cut[w] = nl ? (size_t)(nl - bt.data()) + 1 : bt.size();
+		const auto t1 = t_now();
+		// ---- BLAST(+lineage) table: id, lineage tokens, similarity text per line (Consensus:110-122)
+		std::unordered_map<std::string, uint32_t> tmap;
+		std::vector<std::string> ttext;
+		intern_into(tmap, ttext, "");
+		// Nothing is copied per line: lines and their id are spans of the file text.  Pass A (all host cores, contiguous
+		// pieces of the file): line boundaries, the first three columns of split(/\t\t|\t/) and a 64-bit hash of the
+		// lineage and similarity texts.  Pass B (one thread): the lineage column is tokenised once per DISTINCT text (a
+		// hit table names a few hundred thousand lineages millions of times) and the similarity column ranked once per
+		// distinct text; equal hashes are confirmed by comparing the texts.
+		struct Span {
+			size_t s, n;
+		};
+		struct LineInfo {
+			size_t s;
+			uint32_t n, id_n, lin_s, lin_n, sim_s, sim_n; // column offsets are relative to the line start
+			uint64_t lin_h, sim_h;
+		};
+		auto fnv64 = [](const char *p, size_t n) {
+			uint64_t h = 1469598103934665603ull;
+			for (size_t i = 0; i < n; i++)
+				h = (h ^ (unsigned char)p[i]) * 1099511628211ull;
+			return h;
+		};
+		const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+		const unsigned workers = (unsigned)std::max<size_t>(1, std::min<size_t>(hw, bt.size() / (4u << 20) + 1));
+		std::vector<std::vector<LineInfo>> part(workers);
+		{
+			// piece w = [cut[w], cut[w+1]) where every cut is a line start
+			std::vector<size_t> cut(workers + 1, bt.size());
+			cut[0] = 0;
+			for (unsigned w = 1; w < workers; w++) {
+				size_t c = bt.size() * w / workers;
+				const char *nl = c < bt.size() ? (const char *)memchr(bt.data() + c, '\n', bt.size() - c) : nullptr;
+				cut[w] = nl ? (size_t)(nl - bt.data()) + 1 : bt.size();
+			}
+			auto scan = [&](unsigned w) {
+				std::vector<LineInfo> &out = part[w];
+				out.reserve((cut[w + 1] - cut[w]) / 60 + 16);
+				for (size_t s = cut[w]; s < cut[w + 1];) {
+					const char *nl = (const char *)memchr(bt.data() + s, '\n', bt.size() - s);
+					const size_t e = nl ? (size_t)(nl - bt.data()) : bt.size();
+					const char *ln = bt.data() + s;
+					const size_t n = e - s;
+					// split(/\t\t|\t/): fields 0, 1, 2 in place (a trailing empty field does not exist)
+					Span f[3] = { { 0, 0 }, { 0, 0 }, { 0, 0 } };
+					int nf = 0;
+					size_t a = 0, i = 0;
+					while (i < n && nf < 3) {
+						if (ln[i] == '\t') {
+							f[nf++] = { a, i - a };
+							i += (i + 1 < n && ln[i + 1] == '\t') ? 2 : 1;
+							a = i;
+						} else {
+							i++;
+						}
+					}
+					if (nf < 3 && n > 0 && a < n)
+						f[nf++] = { a, n - a };
+					LineInfo li;
+					li.s = s;
+					li.n = (uint32_t)n;
+					li.id_n = (uint32_t)f[0].n;
+					li.lin_s = (uint32_t)f[1].s;
+					li.lin_n = (uint32_t)f[1].n;
+					li.sim_s = (uint32_t)f[2].s;
+					li.sim_n = (uint32_t)f[2].n;
+					li.lin_h = fnv64(ln + f[1].s, f[1].n);
+					li.sim_h = fnv64(ln + f[2].s, f[2].n);
+					out.push_back(li);
+					s = e + 1;
+				}
+			};
+			if (workers == 1) {
+				scan(0);
+			} else {
+				std::vector<std::thread> th;
+				for (unsigned w = 0; w < workers; w++)
+					th.emplace_back(scan, w);
+				for (auto &t : th)
+					t.join();
+			}
 		}
-		auto scan = [&](unsigned w) {
-			std::vector<LineInfo> &out = part[w];
-			out.reserve((cut[w + 1] - cut[w]) / 60 + 16);
-			for (size_t s = cut[w]; s < cut[w + 1];) {
-				const char *nl = (const char *)memchr(bt.data() + s, '\n', bt.size() - s);
-				const size_t e = nl ? (size_t)(nl - bt.data()) : bt.size();
-				const char *ln = bt.data() + s;
-				const size_t n = e - s;
-				// split(/\t\t|\t/): fields 0, 1, 2 in place (a trailing empty field does not exist)
-				Span f[3] = { { 0, 0 }, { 0, 0 }, { 0, 0 } };
-				int nf = 0;
-				size_t a = 0, i = 0;
-				while (i < n && nf < 3) {
-					if (ln[i] == '\t') {
-						f[nf++] = { a, i - a };
-						i += (i + 1 < n && ln[i + 1] == '\t') ? 2 : 1;
-						a = i;
-					} else {
-						i++;
+		size_t n_lines = 0;
+		for (auto &v : part)
+			n_lines += v.size();
+		std::vector<Span> bline, bid;
+		bline.reserve(n_lines);
+		bid.reserve(n_lines);
+		std::vector<uint32_t> tok_off(1, 0), tok;
+		tok.reserve(n_lines * 14);
+		std::vector<std::string> tk;
+		struct Memo {
+			size_t s;
+			uint32_t n, first, count; // representative text (file offset, length), its tokens in lin_tok
+		};
+		std::unordered_multimap<uint64_t, Memo> lin_memo;
+		std::vector<uint32_t> lin_tok;
+		struct SimMemo {
+			size_t s;
+			uint32_t n, id;
+		};
+		std::unordered_multimap<uint64_t, SimMemo> sim_memo;
+		std::vector<std::string> sim_text;
+		std::vector<uint32_t> line_simid;
+		line_simid.reserve(n_lines);
+		for (auto &v : part) {
+			for (const LineInfo &li : v) {
+				bline.push_back({ li.s, li.n });
+				bid.push_back({ li.s, li.id_n });
+				const char *simp = bt.data() + li.s + li.sim_s, *linp = bt.data() + li.s + li.lin_s;
+				uint32_t sid = 0xFFFFFFFFu;
+				for (auto r = sim_memo.equal_range(li.sim_h); r.first != r.second; ++r.first)
+					if (r.first->second.n == li.sim_n && memcmp(bt.data() + r.first->second.s, simp, li.sim_n) == 0) {
+						sid = r.first->second.id;
+						break;
+					}
+				if (sid == 0xFFFFFFFFu) {
+					sid = (uint32_t)sim_text.size();
+					sim_text.emplace_back(simp, li.sim_n);
+					sim_memo.emplace(li.sim_h, SimMemo{ li.s + li.sim_s, li.sim_n, sid });
+				}
+				line_simid.push_back(sid);
+				const Memo *m = nullptr;
+				for (auto r = lin_memo.equal_range(li.lin_h); r.first != r.second; ++r.first)
+					if (r.first->second.n == li.lin_n && memcmp(bt.data() + r.first->second.s, linp, li.lin_n) == 0) {
+						m = &r.first->second;
+						break;
+					}
+				if (!m) {
+					lineage_tokens(std::string(linp, li.lin_n), tk);
+					const uint32_t t0 = (uint32_t)lin_tok.size();
+					for (auto &t : tk)
+						lin_tok.push_back(intern_into(tmap, ttext, t));
+					m = &lin_memo.emplace(li.lin_h, Memo{ li.s + li.lin_s, li.lin_n, t0, (uint32_t)tk.size() })->second;
+				}
+				tok.insert(tok.end(), lin_tok.begin() + m->first, lin_tok.begin() + m->first + m->count);
+				tok_off.push_back((uint32_t)tok.size());
+			}
+			std::vector<LineInfo>().swap(v);
+		}
+		std::map<std::string, uint32_t> simrank;
+		build_sim_ranks(sim_text, simrank);
+		std::vector<uint32_t> simid_rank(sim_text.size());
+		for (size_t i = 0; i < sim_text.size(); i++)
+			simid_rank[i] = simrank[sim_text[i]];
+		std::vector<uint32_t> line_sim(bline.size());
+		for (size_t i = 0; i < bline.size(); i++)
+			line_sim[i] = simid_rank[line_simid[i]];
+		auto id_equals = [&](size_t line, const std::string &x) {
+			return bid[line].n == x.size() && memcmp(bt.data() + bid[line].s, x.data(), x.size()) == 0;
+		};
+
+		const auto t2 = t_now();
+		// ---- RDP lines (Consensus:126-132) and the cursor walk over both files (Consensus:96-240)
+		std::vector<uint32_t> rdp_off(1, 0), rdp_name;
+		std::vector<int8_t> rdp_rank;
+		std::vector<uint32_t> g_first, g_count, g_rdp, g_init;
+		size_t cur = 0;
+		int found = -1; // undef
+		bool sim_is_undef = true;
+		int status = 0;
+		uint32_t rdp_index = 0;
+		for (size_t s = 0; s < rt.size() && status == 0;) {
+			size_t e = rt.find('\n', s);
+			if (e == std::string::npos)
+				e = rt.size();
+			std::string line(rt, s, e - s);
+			s = e + 1;
+			size_t five = line.find("\t\t\t\t\t");
+			std::string rid = five == std::string::npos ? line : line.substr(0, five);
+			if (five != std::string::npos) {
+				std::string rest = line.substr(five + 5);
+				size_t again = rest.find("\t\t\t\t\t");
+				if (again != std::string::npos)
+					rest.resize(again);
+				std::vector<std::string> f;
+				if (!rest.empty()) {
+					for (size_t a = 0; a <= rest.size();) {
+						size_t t = rest.find('\t', a);
+						if (t == std::string::npos)
+							t = rest.size();
+						f.emplace_back(rest, a, t - a);
+						a = t + 1;
 					}
 				}
-				if (nf < 3 && n > 0 && a < n)
-					f[nf++] = { a, n - a };
-				LineInfo li;
-				li.s = s;
-				li.n = (uint32_t)n;
-				li.id_n = (uint32_t)f[0].n;
-				li.lin_s = (uint32_t)f[1].s;
-				li.lin_n = (uint32_t)f[1].n;
-				li.sim_s = (uint32_t)f[2].s;
-				li.sim_n = (uint32_t)f[2].n;
-				li.lin_h = fnv64(ln + f[1].s, f[1].n);
-				li.sim_h = fnv64(ln + f[2].s, f[2].n);
-				out.push_back(li);
-				s = e + 1;
-			}
-		};
-		if (workers == 1) {
-			scan(0);
-		} else {
-			std::vector<std::thread> th;
-			for (unsigned w = 0; w < workers; w++)
-				th.emplace_back(scan, w);
-			for (auto &t : th)
-				t.join();
-		}
-	}
-	size_t n_lines = 0;
-	for (auto &v : part)
-		n_lines += v.size();
-	std::vector<Span> bline, bid;
-	bline.reserve(n_lines);
-	bid.reserve(n_lines);
-	std::vector<uint32_t> tok_off(1, 0), tok;
-	tok.reserve(n_lines * 14);
-	std::vector<std::string> tk;
-	struct Memo {
-		size_t s;
-		uint32_t n, first, count; // representative text (file offset, length), its tokens in lin_tok
-	};
-	std::unordered_multimap<uint64_t, Memo> lin_memo;
-	std::vector<uint32_t> lin_tok;
-	struct SimMemo {
-		size_t s;
-		uint32_t n, id;
-	};
-	std::unordered_multimap<uint64_t, SimMemo> sim_memo;
-	std::vector<std::string> sim_text;
-	std::vector<uint32_t> line_simid;
-	line_simid.reserve(n_lines);
-	for (auto &v : part) {
-		for (const LineInfo &li : v) {
-			bline.push_back({ li.s, li.n });
-			bid.push_back({ li.s, li.id_n });
-			const char *simp = bt.data() + li.s + li.sim_s, *linp = bt.data() + li.s + li.lin_s;
-			uint32_t sid = 0xFFFFFFFFu;
-			for (auto r = sim_memo.equal_range(li.sim_h); r.first != r.second; ++r.first)
-				if (r.first->second.n == li.sim_n && memcmp(bt.data() + r.first->second.s, simp, li.sim_n) == 0) {
-					sid = r.first->second.id;
-					break;
+				while (!f.empty() && f.back().empty())
+					f.pop_back();
+				for (size_t k = 0; k < f.size(); k += 3) {
+					rdp_name.push_back(intern_into(tmap, ttext, clean_rdp_name(f[k])));
+					rdp_rank.push_back(k + 1 < f.size() ? rdp_rank_index(f[k + 1]) : (int8_t)-1);
 				}
-			if (sid == 0xFFFFFFFFu) {
-				sid = (uint32_t)sim_text.size();
-				sim_text.emplace_back(simp, li.sim_n);
-				sim_memo.emplace(li.sim_h, SimMemo{ li.s + li.sim_s, li.sim_n, sid });
 			}
-			line_simid.push_back(sid);
-			const Memo *m = nullptr;
-			for (auto r = lin_memo.equal_range(li.lin_h); r.first != r.second; ++r.first)
-				if (r.first->second.n == li.lin_n && memcmp(bt.data() + r.first->second.s, linp, li.lin_n) == 0) {
-					m = &r.first->second;
-					break;
+			rdp_off.push_back((uint32_t)rdp_name.size());
+			// GETBLAST loop
+			uint32_t first = (uint32_t)cur, count = 0;
+			for (;;) {
+				const bool have = cur < bline.size();
+				if (have ? id_equals(cur, rid) : rid.empty()) {
+					if (!have) {
+						status = fail(PGX_E_REFHANG, "RDP line %u has an empty id after the BLAST table ends: the reference never terminates", rdp_index + 1);
+						break;
+					}
+					if (count == 0)
+						first = (uint32_t)cur;
+					found = 1;
+					count++;
+					cur++;
+					continue;
 				}
-			if (!m) {
-				lineage_tokens(std::string(linp, li.lin_n), tk);
-				const uint32_t t0 = (uint32_t)lin_tok.size();
-				for (auto &t : tk)
-					lin_tok.push_back(intern_into(tmap, ttext, t));
-				m = &lin_memo.emplace(li.lin_h, Memo{ li.s + li.lin_s, li.lin_n, t0, (uint32_t)tk.size() })->second;
+				if (found == 0) {
+					const std::string id = have ? std::string(bt, bid[cur].s, bid[cur].n) : std::string();
+					log.printf("not found: %s\t %s\n", id.c_str(), rid.c_str()); // Consensus:217
+					if (!have) {
+						status = fail(PGX_E_REFHANG, "RDP read %s has no BLAST lines at or after the cursor: the reference never terminates (SURVEY 3.5)", rid.c_str());
+						break;
+					}
+					cur++;
+					continue;
+				}
+				if (found == 1) {
+					g_first.push_back(first);
+					g_count.push_back(count);
+					g_rdp.push_back(rdp_index);
+					g_init.push_back(sim_is_undef ? simrank[""] : simrank["0"]);
+					sim_is_undef = false;
+					found = 0;
+				}
+				break;
 			}
-			tok.insert(tok.end(), lin_tok.begin() + m->first, lin_tok.begin() + m->first + m->count);
-			tok_off.push_back((uint32_t)tok.size());
+			rdp_index++;
 		}
-		std::vector<LineInfo>().swap(v);
-	}
-	std::map<std::string, uint32_t> simrank;
-	build_sim_ranks(sim_text, simrank);
-	std::vector<uint32_t> simid_rank(sim_text.size());
-	for (size_t i = 0; i < sim_text.size(); i++)
-		simid_rank[i] = simrank[sim_text[i]];
-	std::vector<uint32_t> line_sim(bline.size());
-	for (size_t i = 0; i < bline.size(); i++)
-		line_sim[i] = simid_rank[line_simid[i]];
-	auto id_equals = [&](size_t line, const std::string &x) {
-		return bid[line].n == x.size() && memcmp(bt.data() + bid[line].s, x.data(), x.size()) == 0;
-	};
 
-	const auto t2 = t_now();
-	// ---- RDP lines (Consensus:126-132) and the cursor walk over both files (Consensus:96-240)
-	std::vector<uint32_t> rdp_off(1, 0), rdp_name;
-	std::vector<int8_t> rdp_rank;
-	std::vector<uint32_t> g_first, g_count, g_rdp, g_init;
-	size_t cur = 0;
-	int found = -1; // undef
-	bool sim_is_undef = true;
-	int status = 0;
-	uint32_t rdp_index = 0;
-	for (size_t s = 0; s < rt.size() && status == 0;) {
-		size_t e = rt.find('\n', s);
-		if (e == std::string::npos)
-			e = rt.size();
-		std::string line(rt, s, e - s);
-		s = e + 1;
-		size_t five = line.find("\t\t\t\t\t");
-		std::string rid = five == std::string::npos ? line : line.substr(0, five);
-		if (five != std::string::npos) {
-			std::string rest = line.substr(five + 5);
-			size_t again = rest.find("\t\t\t\t\t");
-			if (again != std::string::npos)
-				rest.resize(again);
-			std::vector<std::string> f;
-			if (!rest.empty()) {
-				for (size_t a = 0; a <= rest.size();) {
-					size_t t = rest.find('\t', a);
-					if (t == std::string::npos)
-						t = rest.size();
-					f.emplace_back(rest, a, t - a);
-					a = t + 1;
-				}
-			}
-			while (!f.empty() && f.back().empty())
-				f.pop_back();
-			for (size_t k = 0; k < f.size(); k += 3) {
-				rdp_name.push_back(intern_into(tmap, ttext, clean_rdp_name(f[k])));
-				rdp_rank.push_back(k + 1 < f.size() ? rdp_rank_index(f[k + 1]) : (int8_t)-1);
-			}
-		}
-		rdp_off.push_back((uint32_t)rdp_name.size());
-		// GETBLAST loop
-		uint32_t first = (uint32_t)cur, count = 0;
-		for (;;) {
-			const bool have = cur < bline.size();
-			if (have ? id_equals(cur, rid) : rid.empty()) {
-				if (!have) {
-					status = fail(PGX_E_REFHANG, "RDP line %u has an empty id after the BLAST table ends: the reference never terminates", rdp_index + 1);
-					break;
-				}
-				if (count == 0)
-					first = (uint32_t)cur;
-				found = 1;
-				count++;
-				cur++;
-				continue;
-			}
-			if (found == 0) {
-				const std::string id = have ? std::string(bt, bid[cur].s, bid[cur].n) : std::string();
-				log.printf("not found: %s\t %s\n", id.c_str(), rid.c_str()); // Consensus:217
-				if (!have) {
-					status = fail(PGX_E_REFHANG, "RDP read %s has no BLAST lines at or after the cursor: the reference never terminates (SURVEY 3.5)", rid.c_str());
-					break;
-				}
-				cur++;
-				continue;
-			}
-			if (found == 1) {
-				g_first.push_back(first);
-				g_count.push_back(count);
-				g_rdp.push_back(rdp_index);
-				g_init.push_back(sim_is_undef ? simrank[""] : simrank["0"]);
-				sim_is_undef = false;
-				found = 0;
-			}
-			break;
-		}
-		rdp_index++;
-	}
-
-	const auto t3 = t_now();
-	// ---- device: agreement counts + arg-max per group
-	const size_t ng = g_first.size();
-	std::vector<pgx_consensus_rec> recs(ng);
-	if (ng) {
-		std::vector<int8_t> tok_rank(ttext.size());
-		for (size_t t = 0; t < ttext.size(); t++)
-			tok_rank[t] = blast_rank_index(ttext[t]);
-		DevBuf<uint32_t> d_first, d_count, d_grdp, d_init, d_toff, d_tok, d_sim, d_roff, d_rname;
-		DevBuf<int8_t> d_trank, d_rrank;
-		DevBuf<pgx_consensus_rec> d_recs;
-		auto up32 = [&](DevBuf<uint32_t> &d, const std::vector<uint32_t> &h) {
-			int q = d.alloc(h.size() ? h.size() : 1);
-			return q < 0 ? q : d.upload(h.data(), h.size());
-		};
-		auto up8 = [&](DevBuf<int8_t> &d, const std::vector<int8_t> &h) {
-			int q = d.alloc(h.size() ? h.size() : 1);
-			return q < 0 ? q : d.upload(h.data(), h.size());
-		};
-		rc = up32(d_first, g_first);
-		if (rc == 0) rc = up32(d_count, g_count);
-		if (rc == 0) rc = up32(d_grdp, g_rdp);
-		if (rc == 0) rc = up32(d_init, g_init);
-		if (rc == 0) rc = up32(d_toff, tok_off);
-		if (rc == 0) rc = up32(d_tok, tok);
-		if (rc == 0) rc = up32(d_sim, line_sim);
-		if (rc == 0) rc = up32(d_roff, rdp_off);
-		if (rc == 0) rc = up32(d_rname, rdp_name);
-		if (rc == 0) rc = up8(d_trank, tok_rank);
-		if (rc == 0) rc = up8(d_rrank, rdp_rank);
-		if (rc == 0) rc = d_recs.alloc(ng);
-		if (rc == 0) {
+		const auto t3 = t_now();
+		// ---- device: agreement counts + arg-max per group
+		const size_t ng = g_first.size();
+		std::vector<pgx_consensus_rec> recs(ng);
+		if (ng) {
+			std::vector<int8_t> tok_rank(ttext.size());
+			for (size_t t = 0; t < ttext.size(); t++)
+				tok_rank[t] = blast_rank_index(ttext[t]);
+			DevBuf<uint32_t> d_first, d_count, d_grdp, d_init, d_toff, d_tok, d_sim, d_roff, d_rname;
+			DevBuf<int8_t> d_trank, d_rrank;
+			DevBuf<pgx_consensus_rec> d_recs;
+			PGX_TRY(d_first.assign(g_first));
+			PGX_TRY(d_count.assign(g_count));
+			PGX_TRY(d_grdp.assign(g_rdp));
+			PGX_TRY(d_init.assign(g_init));
+			PGX_TRY(d_toff.assign(tok_off));
+			PGX_TRY(d_tok.assign(tok));
+			PGX_TRY(d_sim.assign(line_sim));
+			PGX_TRY(d_roff.assign(rdp_off));
+			PGX_TRY(d_rname.assign(rdp_name));
+			PGX_TRY(d_trank.assign(tok_rank));
+			PGX_TRY(d_rrank.assign(rdp_rank));
+			PGX_TRY(d_recs.alloc(ng));
 			hipLaunchKernelGGL(k_consensus_groups, dim3((unsigned)((ng + 63) / 64)), dim3(64), 0, 0, d_first.data(),
 					   d_count.data(), d_grdp.data(), d_init.data(), (uint32_t)ng, d_toff.data(), d_tok.data(),
 					   d_trank.data(), d_sim.data(), d_roff.data(), d_rname.data(), d_rrank.data(), d_recs.data());
 			if (hipGetLastError() != hipSuccess)
-				rc = fail(PGX_E_NODEVICE, "k_consensus_groups launch failed");
+				return fail(PGX_E_NODEVICE, "k_consensus_groups launch failed");
+			PGX_TRY(d_recs.download(recs.data(), ng));
 		}
-		if (rc == 0) rc = d_recs.download(recs.data(), ng);
-		if (rc < 0)
-			return done(rc);
-	}
-	std::string out;
-	for (size_t g = 0; g < ng; g++) {
-		if (recs[g].hit >= 0)
-			out.append(bt, bline[(size_t)recs[g].hit].s, bline[(size_t)recs[g].hit].n);
-		out += "\n";
-		char tmp[64];
-		snprintf(tmp, sizeof tmp, "#Matches found: %d\n", recs[g].matches);
-		out += tmp;
-	}
-	const auto t4 = t_now();
-	int wrc = write_text_file(o, out);
-	if (wrc < 0) {
-		log.printf("Error: Unable to open output file %s.\n", o);
-		return done(wrc);
-	}
-	if (trace)
-		fprintf(stderr, "[pgx trace] consensus verb: files %.0f ms, hit table %.0f ms, RDP + cursor walk %.0f ms, device + text %.0f ms, write %.0f ms\n",
-			t_ms(t0, t1), t_ms(t1, t2), t_ms(t2, t3), t_ms(t3, t4), t_ms(t4, t_now()));
-	if (status == 0)
-		log.s += "\nDone!\n"; // Consensus:242
-	return done(status);
+		std::string out;
+		for (size_t g = 0; g < ng; g++) {
+			if (recs[g].hit >= 0)
+				out.append(bt, bline[(size_t)recs[g].hit].s, bline[(size_t)recs[g].hit].n);
+			out += "\n";
+			char tmp[64];
+			snprintf(tmp, sizeof tmp, "#Matches found: %d\n", recs[g].matches);
+			out += tmp;
+		}
+		const auto t4 = t_now();
+		int wrc = write_text_file(o, out);
+		if (wrc < 0) {
+			log.printf("Error: Unable to open output file %s.\n", o);
+			return wrc;
+		}
+		if (trace)
+			fprintf(stderr, "[pgx trace] consensus verb: files %.0f ms, hit table %.0f ms, RDP + cursor walk %.0f ms, device + text %.0f ms, write %.0f ms\n",
+				t_ms(t0, t1), t_ms(t1, t2), t_ms(t2, t3), t_ms(t3, t4), t_ms(t4, t_now()));
+		if (status == 0)
+			log.s += "\nDone!\n"; // Consensus:242
+		return status;
+	});
 }
 }

@@ -736,28 +736,27 @@ int pgx_blastn_run(const pgx_blastn_opts *o)
 	if (o->outfmt != 6)
 		return fail(PGX_E_ARG, "blastn: only -outfmt 6 is implemented");
 	PGX_TRY(require_device());
-	pgx_db *db = nullptr;
-	PGX_TRY(pgx_db_open(o->db_prefix, &db));
+	pgx_db *opened = nullptr;
+	PGX_TRY(pgx_db_open(o->db_prefix, &opened));
+	const std::unique_ptr<pgx_db> db(opened);
 	db->ungapped = o->ungapped != 0;
 	db->dust = o->no_dust == 0;
 	// (a rank outside [0, world_size) used to write an empty file and succeed)
-	if (o->world_size > 0 && (o->rank < 0 || o->rank >= o->world_size)) {
-		pgx_db_close(db);
+	if (o->world_size > 0 && (o->rank < 0 || o->rank >= o->world_size))
 		return fail(PGX_E_ARG, "blastn: rank %d is outside [0, %d)", o->rank, o->world_size);
-	}
 	// read sharding (mpiblastn's static query partition, Scripts/submit_MPI-blast.job:24): this
 	// process takes block `rank` of `world_size` contiguous blocks
 	int ws = o->world_size > 0 ? o->world_size : 1, rk = o->rank;
-	int rc = 0;
 	const int64_t total = fasta_count_records(o->query_path);
 	if (total < 0)
-		rc = fail(PGX_E_IO, "cannot open query file %s", o->query_path);
+		return fail(PGX_E_IO, "cannot open query file %s", o->query_path);
 	const int64_t lo = total > 0 ? total * rk / ws : 0, hi = total > 0 ? total * (rk + 1) / ws : 0;
-	FILE *fo = nullptr, *fq = nullptr;
-	if (rc == 0 && !(fo = fopen(o->out_path, "wb")))
-		rc = fail(PGX_E_IO, "cannot open %s for writing", o->out_path);
-	if (rc == 0 && !(fq = fopen(o->query_path, "rb")))
-		rc = fail(PGX_E_IO, "cannot open query file %s", o->query_path);
+	FilePtr fo(fopen(o->out_path, "wb"));
+	if (!fo)
+		return fail(PGX_E_IO, "cannot open %s for writing", o->out_path);
+	const FilePtr fq(fopen(o->query_path, "rb"));
+	if (!fq)
+		return fail(PGX_E_IO, "cannot open query file %s", o->query_path);
 	// The query file is streamed in pieces of about 1 GiB that end at a record boundary: each piece is one resident
 	// batch (split + packed on the device, searched, its table rendered on the device and appended to the output),
 	// so neither the file nor the hit table has to fit anywhere at once.
@@ -765,12 +764,12 @@ int pgx_blastn_run(const pgx_blastn_opts *o)
 	std::string carry;
 	int64_t seen = 0; // records in front of the current piece
 	bool eof = false;
-	while (rc == 0 && !eof && seen < hi) {
+	while (!eof && seen < hi) {
 		std::string piece = std::move(carry);
 		carry.clear();
 		const size_t old = piece.size();
 		piece.resize(old + piece_bytes);
-		const size_t got = fread(&piece[old], 1, piece_bytes, fq);
+		const size_t got = fread(&piece[old], 1, piece_bytes, fq.get());
 		piece.resize(old + got);
 		eof = got < piece_bytes;
 		if (!eof) {
@@ -790,35 +789,32 @@ int pgx_blastn_run(const pgx_blastn_opts *o)
 			// a batch whose hit table does not fit (2^32 slots, or HBM) is halved until it does: reads that hit
 			// tens of thousands of subjects each need small batches, ordinary reads take the whole piece
 			const auto text = std::make_shared<const TextBlob>(std::move(piece));
-			std::function<int(int64_t, int64_t)> run = [&](int64_t first, int64_t count) -> int {
-				pgx_reads *rd = nullptr;
-				pgx_hits *h = nullptr;
-				int q = reads_from_fasta_text(text, first, count, false, nullptr, &rd);
-				if (q == 0)
-					q = pgx_blast_search(db, rd, &h);
-				const bool searched = q == 0; // nothing of this batch has been written yet if the search failed
-				if (q == 0)
-					q = format_hits_stream(h, db, rd, [&](const char *p, size_t n) {
-						return fwrite(p, 1, n, fo) == n ? 0 : fail(PGX_E_IO, "short write to %s", o->out_path);
-					});
-				pgx_hits_close(h);
-				pgx_reads_close(rd);
-				if (!searched && (q == PGX_E_LIMIT || q == PGX_E_NOMEM) && count > 1) {
-					q = run(first, count / 2);
-					if (q == 0)
-						q = run(first + count / 2, count - count / 2);
-				}
-				return q;
+			// (`searched`: nothing of the batch has been written yet while it is false)
+			auto batch = [&](int64_t first, int64_t count, bool &searched) -> int {
+				std::unique_ptr<pgx_reads> rd;
+				PGX_TRY(reads_from_fasta_text(text, first, count, false, nullptr, rd));
+				pgx_hits *found = nullptr;
+				PGX_TRY(pgx_blast_search(db.get(), rd.get(), &found));
+				const std::unique_ptr<pgx_hits> h(found);
+				searched = true;
+				return format_hits_stream(h.get(), db.get(), rd.get(), [&](const char *p, size_t n) {
+					return fwrite(p, 1, n, fo.get()) == n ? 0 : fail(PGX_E_IO, "short write to %s", o->out_path);
+				});
 			};
-			rc = run(a - seen, b - a);
+			std::function<int(int64_t, int64_t)> run = [&](int64_t first, int64_t count) -> int {
+				bool searched = false;
+				const int q = batch(first, count, searched);
+				if (searched || (q != PGX_E_LIMIT && q != PGX_E_NOMEM) || count <= 1)
+					return q;
+				PGX_TRY(run(first, count / 2));
+				return run(first + count / 2, count - count / 2);
+			};
+			PGX_TRY(run(a - seen, b - a));
 		}
 		seen += here;
 	}
-	if (fq)
-		fclose(fq);
-	if (fo && fclose(fo) != 0 && rc == 0)
-		rc = fail(PGX_E_IO, "cannot close %s", o->out_path);
-	pgx_db_close(db);
-	return rc;
+	if (fclose(fo.release()) != 0)
+		return fail(PGX_E_IO, "cannot close %s", o->out_path);
+	return 0;
 }
 }

@@ -2325,13 +2325,9 @@ int pgx_blast_search(pgx_db *db, pgx_reads *reads, pgx_hits **out)
 {
 	if (!db || !reads || !out)
 		return fail(PGX_E_ARG, "pgx_blast_search: null argument");
-	pgx_hits *h = new pgx_hits();
-	int rc = search_pipeline(db, reads, nullptr, h, nullptr);
-	if (rc < 0) {
-		delete h;
-		return rc;
-	}
-	*out = h;
+	std::unique_ptr<pgx_hits> h(new pgx_hits());
+	PGX_TRY(search_pipeline(db, reads, nullptr, h.get(), nullptr));
+	*out = h.release();
 	return 0;
 }
 
@@ -2346,22 +2342,17 @@ int pgx_classify_consensus(pgx_db *db, pgx_reads *reads, const pgx_rdp *rdp, pgx
 		PGX_TRY(workspace_of(db, &ws));
 		PGX_TRY(ws->recs.ensure((size_t)reads->n + 1));
 	}
-	pgx_hits *h = hits_out ? new pgx_hits() : &ws->hits;
-	int rc = search_pipeline(db, reads, rdp, h, ws->recs.data());
-	if (rc == 0 && out) {
+	std::unique_ptr<pgx_hits> own(hits_out ? new pgx_hits() : nullptr); // (else the table stays in the workspace)
+	PGX_TRY(search_pipeline(db, reads, rdp, own ? own.get() : &ws->hits, ws->recs.data()));
+	if (out) {
 		if (cap < reads->n)
-			rc = fail(PGX_E_ARG, "record buffer too small");
-		else
-			rc = ws->recs.download(out, (size_t)reads->n);
+			return fail(PGX_E_ARG, "record buffer too small");
+		PGX_TRY(ws->recs.download(out, (size_t)reads->n));
 		trace_point("pgx_classify_consensus: records downloaded");
 	}
-	if (hits_out) {
-		if (rc < 0)
-			delete h;
-		else
-			*hits_out = h;
-	}
-	return rc;
+	if (hits_out)
+		*hits_out = own.release();
+	return 0;
 }
 
 // BASELINE config 5 (BLAST + SOAP + RDP): the reference's Consensus takes the SOAP classification as a third stream,

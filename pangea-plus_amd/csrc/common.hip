@@ -194,16 +194,38 @@ struct StageRing {
 	hipStream_t stream[kStageWorkers] = {};
 	hipEvent_t done[kStageWorkers][2] = {};
 	bool ready = false;
+	// streams and events belong to a device: destroyed when the process moves to another one, or when init() fails
+	// halfway (the next call then builds them from scratch); the pinned buffers serve any device and are kept
+	void teardown()
+	{
+		for (int w = 0; w < kStageWorkers; w++) {
+			if (stream[w])
+				(void)hipStreamDestroy(stream[w]);
+			stream[w] = nullptr;
+			for (int b = 0; b < 2; b++) {
+				if (done[w][b])
+					(void)hipEventDestroy(done[w][b]);
+				done[w][b] = nullptr;
+			}
+		}
+		ready = false;
+	}
 	int init(int dev)
 	{
 		if (ready && device == dev)
 			return 0;
-		if (ready) // (the process moved to another device: streams and events belong to the old one)
-			for (int w = 0; w < kStageWorkers; w++) {
-				(void)hipStreamDestroy(stream[w]);
-				for (int b = 0; b < 2; b++)
-					(void)hipEventDestroy(done[w][b]);
-			}
+		teardown();
+		const int rc = create();
+		if (rc < 0) {
+			teardown();
+			return rc;
+		}
+		device = dev;
+		ready = true;
+		return 0;
+	}
+	int create()
+	{
 		for (int w = 0; w < kStageWorkers; w++) {
 			for (int b = 0; b < 2; b++) {
 				if (!pin[w][b])
@@ -212,8 +234,6 @@ struct StageRing {
 			}
 			PGX_HIP(hipStreamCreateWithFlags(&stream[w], hipStreamNonBlocking));
 		}
-		device = dev;
-		ready = true;
 		return 0;
 	}
 };
@@ -230,63 +250,65 @@ int staged_copy(char *device_p, char *host_p, size_t bytes, bool to_device)
 	PGX_TRY(g_ring.init(dev));
 	const size_t n_stripes = (bytes + kStageStripe - 1) / kStageStripe;
 	const int workers = (int)std::min<size_t>(kStageWorkers, n_stripes);
-	std::atomic<int> failed{ 0 };
+	std::atomic<bool> failed{ false };
+	hipError_t first_err[kStageWorkers] = {}; // each worker's first failure (a worker writes only its own slot)
 	auto work = [&](int w) {
-		if (hipSetDevice(dev) != hipSuccess) {
-			failed = 1;
+		auto ok = [&](hipError_t e) {
+			if (e != hipSuccess && first_err[w] == hipSuccess) {
+				first_err[w] = e;
+				failed = true;
+			}
+			return e == hipSuccess;
+		};
+		if (!ok(hipSetDevice(dev)))
 			return;
-		}
 		int round = 0;
 		for (size_t k = (size_t)w; k < n_stripes && !failed; k += (size_t)workers, round++) {
 			const int b = round & 1;
 			const size_t o = k * kStageStripe, len = std::min(kStageStripe, bytes - o);
 			char *pin = g_ring.pin[w][b];
-			if (round >= 2 && hipEventSynchronize(g_ring.done[w][b]) != hipSuccess) // the buffer's earlier DMA
-				failed = 1;
+			if (round >= 2) // the buffer's earlier DMA
+				ok(hipEventSynchronize(g_ring.done[w][b]));
 			if (to_device) {
 				memcpy(pin, host_p + o, len);
-				if (hipMemcpyAsync(device_p + o, pin, len, hipMemcpyHostToDevice, g_ring.stream[w]) != hipSuccess)
-					failed = 1;
-				if (hipEventRecord(g_ring.done[w][b], g_ring.stream[w]) != hipSuccess)
-					failed = 1;
+				ok(hipMemcpyAsync(device_p + o, pin, len, hipMemcpyHostToDevice, g_ring.stream[w]));
+				ok(hipEventRecord(g_ring.done[w][b], g_ring.stream[w]));
 			} else {
 				// (the copy out of the pinned buffer needs its DMA finished: stripe k's DMA runs while stripe k - workers' bytes
 				// are copied out)
-				if (hipMemcpyAsync(pin, device_p + o, len, hipMemcpyDeviceToHost, g_ring.stream[w]) != hipSuccess)
-					failed = 1;
-				if (hipEventRecord(g_ring.done[w][b], g_ring.stream[w]) != hipSuccess)
-					failed = 1;
+				ok(hipMemcpyAsync(pin, device_p + o, len, hipMemcpyDeviceToHost, g_ring.stream[w]));
+				ok(hipEventRecord(g_ring.done[w][b], g_ring.stream[w]));
 				if (round >= 1) {
 					const size_t ko = (k - (size_t)workers) * kStageStripe;
-					if (hipEventSynchronize(g_ring.done[w][b ^ 1]) != hipSuccess)
-						failed = 1;
+					ok(hipEventSynchronize(g_ring.done[w][b ^ 1]));
 					memcpy(host_p + ko, g_ring.pin[w][b ^ 1], std::min(kStageStripe, bytes - ko));
 				}
 			}
 		}
 		if (!to_device && round >= 1 && !failed) { // the worker's last stripe
 			const size_t k = (size_t)w + (size_t)(round - 1) * (size_t)workers, o = k * kStageStripe;
-			if (hipEventSynchronize(g_ring.done[w][(round - 1) & 1]) != hipSuccess)
-				failed = 1;
+			ok(hipEventSynchronize(g_ring.done[w][(round - 1) & 1]));
 			memcpy(host_p + o, g_ring.pin[w][(round - 1) & 1], std::min(kStageStripe, bytes - o));
 		}
-		if (hipStreamSynchronize(g_ring.stream[w]) != hipSuccess)
-			failed = 1;
+		ok(hipStreamSynchronize(g_ring.stream[w]));
 	};
 	std::vector<std::thread> th;
 	try {
 		for (int w = 1; w < workers; w++)
 			th.emplace_back(work, w);
 	} catch (...) {
-		failed = 1; // (no thread to be had)
+		failed = true; // (no thread to be had)
 	}
 	if (!failed)
 		work(0);
 	for (auto &t : th)
 		t.join();
-	if (failed)
-		return fail(PGX_E_NODEVICE, "staged copy of %zu bytes failed: %s", bytes, hipGetErrorString(hipGetLastError()));
-	return 0;
+	if (!failed)
+		return 0;
+	for (const hipError_t e : first_err)
+		if (e != hipSuccess)
+			return fail(PGX_E_NODEVICE, "staged copy of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+	return fail(PGX_E_NODEVICE, "staged copy of %zu bytes failed: no copy thread could be started", bytes);
 }
 } // namespace
 

@@ -120,6 +120,13 @@ template <typename T> struct DevBuf {
 			return fail(PGX_E_NODEVICE, "hipMemcpy H2D failed: %s", hipGetErrorString(e));
 		return 0;
 	}
+	// alloc(max(count, 1)) and upload(host, count): a buffer filled from host data
+	int assign(const T *host, size_t count)
+	{
+		PGX_TRY(alloc(count ? count : 1));
+		return upload(host, count);
+	}
+	int assign(const std::vector<T> &host) { return assign(host.data(), host.size()); }
 	int download(T *host, size_t count, size_t first = 0) const
 	{
 		if (count == 0)
@@ -139,6 +146,20 @@ struct Text {
 	void printf(const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 	char *release_malloc(size_t *len) const;
 };
+
+// A verb that hands back a log or report text: `body` may return early anywhere, the text is handed out once after it.
+template <typename F> int with_text(Text &text, char **text_out, F &&body)
+{
+	const int rc = body();
+	if (text_out)
+		*text_out = text.release_malloc(nullptr);
+	return rc;
+}
+
+struct FileCloser {
+	void operator()(FILE *f) const { fclose(f); }
+};
+using FilePtr = std::unique_ptr<FILE, FileCloser>;
 
 std::string read_text_file(const char *path, bool *ok);
 // The bytes of a text: an owned string, or a regular file mapped where the page cache holds it (no copy, no zero-filled

@@ -189,13 +189,13 @@ int db_upload_and_index(pgx_db *db);
 int db_build_blk_info(pgx_db *db);
 void index_check(const pgx_db *db, const char *where);
 int reads_from_fasta_ex(const char *path, int64_t first, int64_t count, bool fold_to_g, std::vector<uint32_t> *amb_count,
-			pgx_reads **out);
-int db_fold_amb_to_g(const pgx_db *src, pgx_db **out);
-int db_read_host(const char *prefix, pgx_db **out);
+			std::unique_ptr<pgx_reads> &out);
+int db_fold_amb_to_g(const pgx_db *src, std::unique_ptr<pgx_db> &out);
+int db_read_host(const char *prefix, std::unique_ptr<pgx_db> &out);
 int64_t fasta_count_records(const char *path);
 int64_t fasta_count_records_text(const char *base, size_t len, bool *at_line_start);
 int reads_from_fasta_text(std::shared_ptr<const TextBlob> text, int64_t first, int64_t count, bool fold_to_g,
-			  std::vector<uint32_t> *amb_count, pgx_reads **out);
+			  std::vector<uint32_t> *amb_count, std::unique_ptr<pgx_reads> &out);
 int db_build_index(pgx_db *db);
 int choose_index_bits(int64_t n_postings);
 

@@ -390,343 +390,311 @@ extern "C" {
 int pgx_megaclust_file(const pgx_megaclust_opts *o, char **log_text)
 {
 	Text log;
-	auto done = [&](int rc) {
-		if (log_text)
-			*log_text = log.release_malloc(nullptr);
-		return rc;
-	};
-	if (!o)
-		return done(fail(PGX_E_ARG, "pgx_megaclust_file: null options"));
-	McParams p;
-	if (mc_params(o, true, p, log)) {
-		log.s += "\n";
-		return done(0);
-	}
-	int rc = require_device();
-	if (rc < 0)
-		return done(rc);
-	bool ok;
-	const std::string text = read_text_file(o->in_path, &ok);
-	if (!ok)
-		return done(fail(PGX_E_IO, "couldn't open infile %s", o->in_path)); // megaclust2.pl:75 dies
-	FILE *probe = fopen(o->out_path, "w");
-	if (!probe)
-		return done(fail(PGX_E_IO, "couldn't open outfile %s", o->out_path)); // :76
-	fclose(probe);
-	// host: lines, columns, interned OTU / query texts, numeric columns as the Perl would numify them
-	std::vector<double> pid, ev, bits;
-	std::vector<uint32_t> otu, query;
-	std::unordered_map<std::string, uint32_t> otu_id, query_id;
-	std::vector<std::string> otu_text, query_text;
-	bool unique_queries = true;
-	for (size_t s = 0; s < text.size();) {
-		const size_t nl = text.find('\n', s);
-		const size_t e = nl == std::string::npos ? text.size() : nl; // chomp: the newline only
-		const char *line = text.data() + s;
-		const size_t n = e - s;
-		s = nl == std::string::npos ? text.size() : e + 1;
-		if (n > 0 && line[0] == '#') // :81
-			continue;
-		Field f[13];
-		mc_split(line, n, f, 13);
-		pid.push_back(f[2].defined ? perl_num(f[2].p, f[2].n) : 0.0);
-		ev.push_back(f[10].defined ? perl_num(f[10].p, f[10].n) : 0.0);
-		bits.push_back(f[11].defined ? perl_num(f[11].p, f[11].n) : 0.0);
-		otu.push_back(intern_text(otu_id, otu_text, f[1].p, f[1].n));
-		bool is_new;
-		query.push_back(intern_text(query_id, query_text, f[0].p, f[0].n, &is_new));
-		if (!is_new)
-			unique_queries = false;
-	}
-	const uint64_t n = pid.size();
-	DevBuf<double> d_pid, d_ev, d_bits;
-	DevBuf<uint32_t> d_otu, d_query;
-	DevBuf<uint8_t> d_pass;
-	rc = d_pid.alloc(n ? n : 1);
-	if (rc == 0) rc = d_ev.alloc(n ? n : 1);
-	if (rc == 0) rc = d_bits.alloc(n ? n : 1);
-	if (rc == 0) rc = d_otu.alloc(n ? n : 1);
-	if (rc == 0) rc = d_query.alloc(n ? n : 1);
-	if (rc == 0) rc = d_pass.alloc(n ? n : 1);
-	if (rc == 0 && n) {
-		rc = d_pid.upload(pid.data(), n);
-		if (rc == 0) rc = d_ev.upload(ev.data(), n);
-		if (rc == 0) rc = d_bits.upload(bits.data(), n);
-		if (rc == 0) rc = d_otu.upload(otu.data(), n);
-		if (rc == 0) rc = d_query.upload(query.data(), n);
-	}
-	if (rc < 0)
-		return done(rc);
-	if (n) {
-		hipLaunchKernelGGL(k_mc_filter_lines, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_pid.data(), d_ev.data(),
-				   d_bits.data(), n, p.sim, p.ev, p.bits, d_pass.data());
-		if (hipGetLastError() != hipSuccess)
-			return done(fail(PGX_E_NODEVICE, "k_mc_filter_lines launch failed"));
-	}
-	McResult res;
-	rc = mc_count(d_pass.data(), nullptr, d_otu.data(), d_query.data(), n, otu_text.size(), p.count_all, unique_queries, res);
-	if (rc < 0)
-		return done(rc);
-	std::string csv;
-	mc_render(res, otu_text, p, csv, log);
-	rc = write_text_file(o->out_path, csv);
-	return done(rc);
+	return with_text(log, log_text, [&]() -> int {
+		if (!o)
+			return fail(PGX_E_ARG, "pgx_megaclust_file: null options");
+		McParams p;
+		if (mc_params(o, true, p, log)) {
+			log.s += "\n";
+			return 0;
+		}
+		PGX_TRY(require_device());
+		bool ok;
+		const std::string text = read_text_file(o->in_path, &ok);
+		if (!ok)
+			return fail(PGX_E_IO, "couldn't open infile %s", o->in_path); // megaclust2.pl:75 dies
+		FILE *probe = fopen(o->out_path, "w");
+		if (!probe)
+			return fail(PGX_E_IO, "couldn't open outfile %s", o->out_path); // :76
+		fclose(probe);
+		// host: lines, columns, interned OTU / query texts, numeric columns as the Perl would numify them
+		std::vector<double> pid, ev, bits;
+		std::vector<uint32_t> otu, query;
+		std::unordered_map<std::string, uint32_t> otu_id, query_id;
+		std::vector<std::string> otu_text, query_text;
+		bool unique_queries = true;
+		for (size_t s = 0; s < text.size();) {
+			const size_t nl = text.find('\n', s);
+			const size_t e = nl == std::string::npos ? text.size() : nl; // chomp: the newline only
+			const char *line = text.data() + s;
+			const size_t n = e - s;
+			s = nl == std::string::npos ? text.size() : e + 1;
+			if (n > 0 && line[0] == '#') // :81
+				continue;
+			Field f[13];
+			mc_split(line, n, f, 13);
+			pid.push_back(f[2].defined ? perl_num(f[2].p, f[2].n) : 0.0);
+			ev.push_back(f[10].defined ? perl_num(f[10].p, f[10].n) : 0.0);
+			bits.push_back(f[11].defined ? perl_num(f[11].p, f[11].n) : 0.0);
+			otu.push_back(intern_text(otu_id, otu_text, f[1].p, f[1].n));
+			bool is_new;
+			query.push_back(intern_text(query_id, query_text, f[0].p, f[0].n, &is_new));
+			if (!is_new)
+				unique_queries = false;
+		}
+		const uint64_t n = pid.size();
+		DevBuf<double> d_pid, d_ev, d_bits;
+		DevBuf<uint32_t> d_otu, d_query;
+		DevBuf<uint8_t> d_pass;
+		PGX_TRY(d_pid.assign(pid));
+		PGX_TRY(d_ev.assign(ev));
+		PGX_TRY(d_bits.assign(bits));
+		PGX_TRY(d_otu.assign(otu));
+		PGX_TRY(d_query.assign(query));
+		PGX_TRY(d_pass.alloc(n ? n : 1));
+		if (n) {
+			hipLaunchKernelGGL(k_mc_filter_lines, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_pid.data(), d_ev.data(),
+					   d_bits.data(), n, p.sim, p.ev, p.bits, d_pass.data());
+			if (hipGetLastError() != hipSuccess)
+				return fail(PGX_E_NODEVICE, "k_mc_filter_lines launch failed");
+		}
+		McResult res;
+		PGX_TRY(mc_count(d_pass.data(), nullptr, d_otu.data(), d_query.data(), n, otu_text.size(), p.count_all, unique_queries, res));
+		std::string csv;
+		mc_render(res, otu_text, p, csv, log);
+		return write_text_file(o->out_path, csv);
+	});
 }
 
 int pgx_megaclust_batch(const pgx_db *db, const pgx_reads *reads, const pgx_hits *hits, const pgx_consensus_rec *recs, int64_t n,
 			const pgx_megaclust_opts *o, char **csv_text, size_t *csv_len, char **log_text)
 {
 	Text log;
-	auto done = [&](int rc) {
-		if (log_text)
-			*log_text = log.release_malloc(nullptr);
-		return rc;
-	};
-	if (csv_text)
-		*csv_text = nullptr;
-	if (!db || !reads || !hits || !recs || !o || !csv_text || n < 0 || n > reads->n)
-		return done(fail(PGX_E_ARG, "pgx_megaclust_batch: bad argument"));
-	if (!db->bound)
-		return done(fail(PGX_E_ARG, "pgx_megaclust_batch: database is not bound to a taxonomy"));
-	McParams p;
-	if (mc_params(o, false, p, log)) {
-		log.s += "\n";
-		return done(0);
-	}
-	int rc = require_device();
-	if (rc < 0)
-		return done(rc);
-	// OTU ids come with the taxonomy binding: one per distinct lineage text, plus one for the empty text
-	const std::vector<std::string> &lin_text = db->lin_text;
-	const uint32_t empty_lin = db->empty_lin;
-	// thresholds as integers.  pident: the text is "%.2f" of hundredths / 100
-	int h_min = 10001;
-	for (int h = 0; h <= 10000; h++) {
-		char buf[16];
-		snprintf(buf, sizeof buf, "%d.%02d", h / 100, h % 100);
-		if (!(perl_num(buf, strlen(buf)) < p.sim)) {
-			h_min = h;
-			break;
+	return with_text(log, log_text, [&]() -> int {
+		if (csv_text)
+			*csv_text = nullptr;
+		if (!db || !reads || !hits || !recs || !o || !csv_text || n < 0 || n > reads->n)
+			return fail(PGX_E_ARG, "pgx_megaclust_batch: bad argument");
+		if (!db->bound)
+			return fail(PGX_E_ARG, "pgx_megaclust_batch: database is not bound to a taxonomy");
+		McParams p;
+		if (mc_params(o, false, p, log)) {
+			log.s += "\n";
+			return 0;
 		}
-	}
-	// e-value and bit score: both texts are functions of (raw score, read length); accepted scores form an
-	// upper range (E falls and the bit score rises with the score, the formats are monotone)
-	const uint32_t max_len = (uint32_t)reads->max_len;
-	std::vector<uint32_t> s_min((size_t)max_len + 1, 0xFFFFFFFFu);
-	{
-		std::vector<uint8_t> seen((size_t)max_len + 1, 0);
-		for (int64_t r = 0; r < n; r++)
-			seen[reads->h_len[(size_t)r]] = 1;
-		std::string evt, bst;
-		auto ok_score = [&](int score, uint32_t L) {
-			format_score_columns(score, L, db->n_bases, db->n_seq, hits->gapped, evt, bst);
-			return !(perl_num(evt) > p.ev) && !(perl_num(bst) < p.bits);
-		};
-		for (uint32_t L = 0; L <= max_len; L++) {
-			if (!seen[L] || L == 0)
-				continue;
-			if (!ok_score((int)L, L))
-				continue; // not even a full-length perfect match passes
-			int lo = 0, hi = (int)L; // hi passes; lowest passing score by bisection
-			while (lo < hi) {
-				const int mid = lo + (hi - lo) / 2;
-				if (ok_score(mid, L))
-					hi = mid;
-				else
-					lo = mid + 1;
+		PGX_TRY(require_device());
+		// OTU ids come with the taxonomy binding: one per distinct lineage text, plus one for the empty text
+		const std::vector<std::string> &lin_text = db->lin_text;
+		const uint32_t empty_lin = db->empty_lin;
+		// thresholds as integers.  pident: the text is "%.2f" of hundredths / 100
+		int h_min = 10001;
+		for (int h = 0; h <= 10000; h++) {
+			char buf[16];
+			snprintf(buf, sizeof buf, "%d.%02d", h / 100, h % 100);
+			if (!(perl_num(buf, strlen(buf)) < p.sim)) {
+				h_min = h;
+				break;
 			}
-			s_min[L] = (uint32_t)hi;
 		}
-	}
-	const int empty_pass = !(0.0 < p.sim || 0.0 > p.ev || 0.0 < p.bits);
-	// query texts: a pair (OTU, query) counts once; only repeated read names need the key sort
-	bool unique_queries = true;
-	std::vector<uint32_t> qid;
-	if (!reads->synthetic && !p.count_all && !ReadNameIndex(*reads).unique) {
-		std::unordered_map<std::string, uint32_t> qmap;
-		std::vector<std::string> qtext;
-		qid.resize((size_t)n);
-		for (int64_t r = 0; r < n; r++) {
-			const std::string nm = reads->name_of(r);
-			bool is_new;
-			qid[(size_t)r] = intern_text(qmap, qtext, nm.data(), nm.size(), &is_new);
-			if (!is_new)
-				unique_queries = false;
+		// e-value and bit score: both texts are functions of (raw score, read length); accepted scores form an
+		// upper range (E falls and the bit score rises with the score, the formats are monotone)
+		const uint32_t max_len = (uint32_t)reads->max_len;
+		std::vector<uint32_t> s_min((size_t)max_len + 1, 0xFFFFFFFFu);
+		{
+			std::vector<uint8_t> seen((size_t)max_len + 1, 0);
+			for (int64_t r = 0; r < n; r++)
+				seen[reads->h_len[(size_t)r]] = 1;
+			std::string evt, bst;
+			auto ok_score = [&](int score, uint32_t L) {
+				format_score_columns(score, L, db->n_bases, db->n_seq, hits->gapped, evt, bst);
+				return !(perl_num(evt) > p.ev) && !(perl_num(bst) < p.bits);
+			};
+			for (uint32_t L = 0; L <= max_len; L++) {
+				if (!seen[L] || L == 0)
+					continue;
+				if (!ok_score((int)L, L))
+					continue; // not even a full-length perfect match passes
+				int lo = 0, hi = (int)L; // hi passes; lowest passing score by bisection
+				while (lo < hi) {
+					const int mid = lo + (hi - lo) / 2;
+					if (ok_score(mid, L))
+						hi = mid;
+					else
+						lo = mid + 1;
+				}
+				s_min[L] = (uint32_t)hi;
+			}
 		}
-	}
-	DevBuf<pgx_consensus_rec> d_recs;
-	DevBuf<uint32_t> d_smin, d_lin, d_qid;
-	DevBuf<uint8_t> d_pass, d_line;
-	const size_t nn = n ? (size_t)n : 1;
-	rc = d_recs.alloc(nn);
-	if (rc == 0) rc = d_smin.alloc(s_min.size());
-	if (rc == 0) rc = d_lin.alloc(nn);
-	if (rc == 0) rc = d_pass.alloc(nn);
-	if (rc == 0) rc = d_line.alloc(nn);
-	if (rc == 0) rc = d_qid.alloc(nn);
-	if (rc == 0 && n) rc = d_recs.upload(recs, (size_t)n);
-	if (rc == 0) rc = d_smin.upload(s_min.data(), s_min.size());
-	if (rc == 0 && !unique_queries) rc = d_qid.upload(qid.data(), (size_t)n);
-	if (rc < 0)
-		return done(rc);
-	if (n) {
-		hipLaunchKernelGGL(k_mc_filter_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_recs.data(), hits->d_hits.data(),
-				   reads->d_len.data(), db->d_subj_lin.data(), (uint64_t)n, h_min, d_smin.data(), max_len, empty_pass, empty_lin,
-				   d_pass.data(), d_line.data(), d_lin.data());
-		if (hipGetLastError() != hipSuccess)
-			return done(fail(PGX_E_NODEVICE, "k_mc_filter_batch launch failed"));
-	}
-	McResult res;
-	rc = mc_count(d_pass.data(), d_line.data(), d_lin.data(), d_qid.data(), (uint64_t)n, lin_text.size(), p.count_all, unique_queries,
-		      res);
-	if (rc < 0)
-		return done(rc);
-	Text csv;
-	mc_render(res, lin_text, p, csv.s, log);
-	*csv_text = csv.release_malloc(csv_len);
-	return done(*csv_text ? 0 : fail(PGX_E_NOMEM, "out of memory"));
+		const int empty_pass = !(0.0 < p.sim || 0.0 > p.ev || 0.0 < p.bits);
+		// query texts: a pair (OTU, query) counts once; only repeated read names need the key sort
+		bool unique_queries = true;
+		std::vector<uint32_t> qid;
+		if (!reads->synthetic && !p.count_all && !ReadNameIndex(*reads).unique) {
+			std::unordered_map<std::string, uint32_t> qmap;
+			std::vector<std::string> qtext;
+			qid.resize((size_t)n);
+			for (int64_t r = 0; r < n; r++) {
+				const std::string nm = reads->name_of(r);
+				bool is_new;
+				qid[(size_t)r] = intern_text(qmap, qtext, nm.data(), nm.size(), &is_new);
+				if (!is_new)
+					unique_queries = false;
+			}
+		}
+		DevBuf<pgx_consensus_rec> d_recs;
+		DevBuf<uint32_t> d_smin, d_lin, d_qid;
+		DevBuf<uint8_t> d_pass, d_line;
+		const size_t nn = n ? (size_t)n : 1;
+		PGX_TRY(d_recs.assign(recs, (size_t)n));
+		PGX_TRY(d_smin.alloc(s_min.size()));
+		PGX_TRY(d_smin.upload(s_min.data(), s_min.size()));
+		PGX_TRY(d_lin.alloc(nn));
+		PGX_TRY(d_pass.alloc(nn));
+		PGX_TRY(d_line.alloc(nn));
+		PGX_TRY(d_qid.alloc(nn));
+		if (!unique_queries)
+			PGX_TRY(d_qid.upload(qid.data(), (size_t)n));
+		if (n) {
+			hipLaunchKernelGGL(k_mc_filter_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_recs.data(), hits->d_hits.data(),
+					   reads->d_len.data(), db->d_subj_lin.data(), (uint64_t)n, h_min, d_smin.data(), max_len, empty_pass, empty_lin,
+					   d_pass.data(), d_line.data(), d_lin.data());
+			if (hipGetLastError() != hipSuccess)
+				return fail(PGX_E_NODEVICE, "k_mc_filter_batch launch failed");
+		}
+		McResult res;
+		PGX_TRY(mc_count(d_pass.data(), d_line.data(), d_lin.data(), d_qid.data(), (uint64_t)n, lin_text.size(), p.count_all, unique_queries,
+				 res));
+		Text csv;
+		mc_render(res, lin_text, p, csv.s, log);
+		*csv_text = csv.release_malloc(csv_len);
+		return *csv_text ? 0 : fail(PGX_E_NOMEM, "out of memory");
+	});
 }
 
 int pgx_megaclustable(int argc, const char *const *argv, char **log_text)
 {
 	Text log;
-	auto done = [&](int rc) {
-		if (log_text)
-			*log_text = log.release_malloc(nullptr);
-		return rc;
-	};
-	if (argc < 0 || (argc > 0 && !argv))
-		return done(fail(PGX_E_ARG, "pgx_megaclustable: bad argument vector"));
-	if (argc - 1 < 5) { // megaclustable.pl:17-21
-		log.s += "Please enter the correct parameters.\n";
-		return done(0);
-	}
-	const char *output = nullptr;
-	std::string level;
-	std::vector<std::string> files;
-	bool m_in = false;
-	for (int a = 0; a < argc; a++) { // :25-52; `$mIN` (:38) is a typo in the script: -t never leaves the file-list mode
-		const std::string arg = argv[a];
-		if (arg == "-m") {
-			m_in = true;
-		} else if (arg == "-o") {
-			m_in = false;
-			a++;
-			output = a < argc ? argv[a] : nullptr;
-		} else if (arg == "-t") {
-			a++;
-			const std::string t = a < argc ? argv[a] : "";
-			const double v = perl_num(t);
-			if (v > 6 || v < 0) {
-				log.s += "You must enter a number between 0 and 6 for taxonomy level where 0 = domain and 6 = species.\n";
-				return done(0);
-			}
-			level = "[" + t + "]";
-		} else if (m_in) {
-			files.push_back(arg);
+	return with_text(log, log_text, [&]() -> int {
+		if (argc < 0 || (argc > 0 && !argv))
+			return fail(PGX_E_ARG, "pgx_megaclustable: bad argument vector");
+		if (argc - 1 < 5) { // megaclustable.pl:17-21
+			log.s += "Please enter the correct parameters.\n";
+			return 0;
 		}
-	}
-	int rc = require_device();
-	if (rc < 0)
-		return done(rc);
-	// host pass: the script's index/substr arithmetic per line; every line becomes (file, taxon, number)
-	std::vector<std::string> taxa;
-	std::unordered_map<std::string, uint32_t> taxon_id;
-	struct Item {
-		uint32_t file, taxon;
-		double val;
-	};
-	std::vector<Item> items;
-	std::vector<size_t> size_at_file;                 // taxa known when each file was opened (cells start as "0")
-	std::map<std::pair<uint32_t, uint32_t>, std::string> raw; // (file, taxon) -> text of the line that introduced the taxon
-	for (size_t b = 0; b < files.size(); b++) {
-		bool ok;
-		const std::string text = read_text_file(files[b].c_str(), &ok);
-		if (!ok) { // :63-67
-			log.printf("Unable to open %s\nMake sure you entered the extension when entering the file name.\n", files[b].c_str());
-			return done(0);
-		}
-		size_at_file.push_back(taxa.size());
-		for (size_t s = 0; s < text.size();) {
-			const size_t nl = text.find('\n', s);
-			const size_t e = nl == std::string::npos ? text.size() : nl;
-			const std::string line = text.substr(s, e - s);
-			s = nl == std::string::npos ? text.size() : e + 1;
-			long loc = p_index(line, level, 0); // :76
-			if (loc < 0)
-				continue;
-			loc += 3;
-			long end = p_index(line, ";", loc);
-			if (end == -1)
-				end = p_index(line, ",", loc);
-			const std::string name = p_substr(line, loc, end - loc);
-			const long num_start = p_index(line, ",", end) + 1;
-			const std::string num = p_substr(line, num_start, (long)line.size() - num_start);
-			auto it = taxon_id.find(name);
-			if (it == taxon_id.end()) { // :98-103: a new taxon keeps the text of its first number
-				const uint32_t id = (uint32_t)taxa.size();
-				taxa.push_back(name);
-				taxon_id.emplace(name, id);
-				raw[{ (uint32_t)b, id }] = num;
-				items.push_back({ (uint32_t)b, id, perl_num(num) });
-			} else {
-				items.push_back({ (uint32_t)b, it->second, perl_num(num) }); // :93 `+=`
+		const char *output = nullptr;
+		std::string level;
+		std::vector<std::string> files;
+		bool m_in = false;
+		for (int a = 0; a < argc; a++) { // :25-52; `$mIN` (:38) is a typo in the script: -t never leaves the file-list mode
+			const std::string arg = argv[a];
+			if (arg == "-m") {
+				m_in = true;
+			} else if (arg == "-o") {
+				m_in = false;
+				a++;
+				output = a < argc ? argv[a] : nullptr;
+			} else if (arg == "-t") {
+				a++;
+				const std::string t = a < argc ? argv[a] : "";
+				const double v = perl_num(t);
+				if (v > 6 || v < 0) {
+					log.s += "You must enter a number between 0 and 6 for taxonomy level where 0 = domain and 6 = species.\n";
+					return 0;
+				}
+				level = "[" + t + "]";
+			} else if (m_in) {
+				files.push_back(arg);
 			}
 		}
-	}
-	// device: cells in (file, taxon) order, each summed in line order
-	const size_t n_files = files.size(), n_taxa = taxa.size(), n_cells = n_files * n_taxa;
-	std::vector<uint32_t> cell_cnt(n_cells + 1, 0), cell_off(n_cells + 1, 0);
-	for (const Item &it : items)
-		cell_cnt[(size_t)it.file * n_taxa + it.taxon]++;
-	for (size_t c = 0; c < n_cells; c++)
-		cell_off[c + 1] = cell_off[c] + cell_cnt[c];
-	std::vector<double> vals(items.size());
-	{
-		std::vector<uint32_t> cur(cell_off.begin(), cell_off.end() - 1);
-		for (const Item &it : items) // stable: line order inside a cell
-			vals[cur[(size_t)it.file * n_taxa + it.taxon]++] = it.val;
-	}
-	std::vector<double> sums(n_cells, 0.0);
-	if (n_cells) {
-		DevBuf<uint32_t> d_off;
-		DevBuf<double> d_val, d_sum;
-		PGX_TRY(d_off.alloc(n_cells + 1));
-		PGX_TRY(d_val.alloc(vals.size() ? vals.size() : 1));
-		PGX_TRY(d_sum.alloc(n_cells));
-		PGX_TRY(d_off.upload(cell_off.data(), n_cells + 1));
-		PGX_TRY(d_val.upload(vals.data(), vals.size()));
-		hipLaunchKernelGGL(k_pivot_cells, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, 0, d_off.data(), d_val.data(),
-				   (uint32_t)n_cells, d_sum.data());
-		PGX_HIP(hipGetLastError());
-		PGX_TRY(d_sum.download(sums.data(), n_cells));
-	}
-	// :111-128
-	if (!output)
-		return done(fail(PGX_E_IO, "megaclustable: no output file"));
-	std::string out;
-	for (size_t a = 1; a <= n_files; a++)
-		out += "\t" + std::to_string(a);
-	for (size_t a = 0; a < n_taxa; a++) {
-		out += "\n";
-		out += taxa[a].empty() ? "0" : taxa[a]; // `eq ""` turns an empty name into 0 (:120-123)
-		out += "\t";
-		for (size_t b = 0; b < n_files; b++) {
-			const size_t c = b * n_taxa + a;
-			const uint32_t k = cell_cnt[c];
-			auto r = raw.find({ (uint32_t)b, (uint32_t)a });
-			std::string cell;
-			if (r != raw.end() && k == 1)
-				cell = r->second.empty() ? "0" : r->second; // pushed as text, never added to
-			else if (k == 0)
-				cell = "0"; // "0" (taxon known when the file was opened) or undef (added by a later file): both print 0
-			else
-				cell = perl_number_text(sums[c]);
-			out += cell;
+		PGX_TRY(require_device());
+		// host pass: the script's index/substr arithmetic per line; every line becomes (file, taxon, number)
+		std::vector<std::string> taxa;
+		std::unordered_map<std::string, uint32_t> taxon_id;
+		struct Item {
+			uint32_t file, taxon;
+			double val;
+		};
+		std::vector<Item> items;
+		std::vector<size_t> size_at_file;                 // taxa known when each file was opened (cells start as "0")
+		std::map<std::pair<uint32_t, uint32_t>, std::string> raw; // (file, taxon) -> text of the line that introduced the taxon
+		for (size_t b = 0; b < files.size(); b++) {
+			bool ok;
+			const std::string text = read_text_file(files[b].c_str(), &ok);
+			if (!ok) { // :63-67
+				log.printf("Unable to open %s\nMake sure you entered the extension when entering the file name.\n", files[b].c_str());
+				return 0;
+			}
+			size_at_file.push_back(taxa.size());
+			for (size_t s = 0; s < text.size();) {
+				const size_t nl = text.find('\n', s);
+				const size_t e = nl == std::string::npos ? text.size() : nl;
+				const std::string line = text.substr(s, e - s);
+				s = nl == std::string::npos ? text.size() : e + 1;
+				long loc = p_index(line, level, 0); // :76
+				if (loc < 0)
+					continue;
+				loc += 3;
+				long end = p_index(line, ";", loc);
+				if (end == -1)
+					end = p_index(line, ",", loc);
+				const std::string name = p_substr(line, loc, end - loc);
+				const long num_start = p_index(line, ",", end) + 1;
+				const std::string num = p_substr(line, num_start, (long)line.size() - num_start);
+				auto it = taxon_id.find(name);
+				if (it == taxon_id.end()) { // :98-103: a new taxon keeps the text of its first number
+					const uint32_t id = (uint32_t)taxa.size();
+					taxa.push_back(name);
+					taxon_id.emplace(name, id);
+					raw[{ (uint32_t)b, id }] = num;
+					items.push_back({ (uint32_t)b, id, perl_num(num) });
+				} else {
+					items.push_back({ (uint32_t)b, it->second, perl_num(num) }); // :93 `+=`
+				}
+			}
+		}
+		// device: cells in (file, taxon) order, each summed in line order
+		const size_t n_files = files.size(), n_taxa = taxa.size(), n_cells = n_files * n_taxa;
+		std::vector<uint32_t> cell_cnt(n_cells + 1, 0), cell_off(n_cells + 1, 0);
+		for (const Item &it : items)
+			cell_cnt[(size_t)it.file * n_taxa + it.taxon]++;
+		for (size_t c = 0; c < n_cells; c++)
+			cell_off[c + 1] = cell_off[c] + cell_cnt[c];
+		std::vector<double> vals(items.size());
+		{
+			std::vector<uint32_t> cur(cell_off.begin(), cell_off.end() - 1);
+			for (const Item &it : items) // stable: line order inside a cell
+				vals[cur[(size_t)it.file * n_taxa + it.taxon]++] = it.val;
+		}
+		std::vector<double> sums(n_cells, 0.0);
+		if (n_cells) {
+			DevBuf<uint32_t> d_off;
+			DevBuf<double> d_val, d_sum;
+			PGX_TRY(d_off.alloc(n_cells + 1));
+			PGX_TRY(d_val.alloc(vals.size() ? vals.size() : 1));
+			PGX_TRY(d_sum.alloc(n_cells));
+			PGX_TRY(d_off.upload(cell_off.data(), n_cells + 1));
+			PGX_TRY(d_val.upload(vals.data(), vals.size()));
+			hipLaunchKernelGGL(k_pivot_cells, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, 0, d_off.data(), d_val.data(),
+					   (uint32_t)n_cells, d_sum.data());
+			PGX_HIP(hipGetLastError());
+			PGX_TRY(d_sum.download(sums.data(), n_cells));
+		}
+		// :111-128
+		if (!output)
+			return fail(PGX_E_IO, "megaclustable: no output file");
+		std::string out;
+		for (size_t a = 1; a <= n_files; a++)
+			out += "\t" + std::to_string(a);
+		for (size_t a = 0; a < n_taxa; a++) {
+			out += "\n";
+			out += taxa[a].empty() ? "0" : taxa[a]; // `eq ""` turns an empty name into 0 (:120-123)
 			out += "\t";
+			for (size_t b = 0; b < n_files; b++) {
+				const size_t c = b * n_taxa + a;
+				const uint32_t k = cell_cnt[c];
+				auto r = raw.find({ (uint32_t)b, (uint32_t)a });
+				std::string cell;
+				if (r != raw.end() && k == 1)
+					cell = r->second.empty() ? "0" : r->second; // pushed as text, never added to
+				else if (k == 0)
+					cell = "0"; // "0" (taxon known when the file was opened) or undef (added by a later file): both print 0
+				else
+					cell = perl_number_text(sums[c]);
+				out += cell;
+				out += "\t";
+			}
 		}
-	}
-	rc = write_text_file(output, out);
-	return done(rc);
+		return write_text_file(output, out);
+	});
 }
 }

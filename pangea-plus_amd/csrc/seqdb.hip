@@ -588,9 +588,9 @@ static void synth_ids(pgx_db *db)
 	}
 }
 
-static int db_from_packed(PackedSet &ps, pgx_db **out)
+static std::unique_ptr<pgx_db> db_from_packed(PackedSet &ps)
 {
-	pgx_db *db = new pgx_db();
+	std::unique_ptr<pgx_db> db(new pgx_db());
 	db->n_seq = (int64_t)ps.headers.size();
 	db->n_bases = (int64_t)ps.off.back();
 	db->has_amb = ps.any_amb;
@@ -601,8 +601,7 @@ static int db_from_packed(PackedSet &ps, pgx_db **out)
 		db->ids.push_back(first_word(h));
 	db->h_words.swap(ps.words);
 	db->h_amb.swap(ps.amb);
-	*out = db;
-	return 0;
+	return db;
 }
 
 // ------------------------------------------------------------------------------------------ .pgxdb file
@@ -629,30 +628,27 @@ static int db_write_file(const pgx_db *db, const char *prefix)
 	return 0;
 }
 
-static int db_read_file(const char *prefix, pgx_db **out)
+static int db_read_file(const char *prefix, std::unique_ptr<pgx_db> &out)
 {
 	std::string path = std::string(prefix) + ".pgxdb";
-	FILE *f = fopen(path.c_str(), "rb");
+	const FilePtr file(fopen(path.c_str(), "rb"));
+	FILE *f = file.get();
 	if (!f)
 		return fail(PGX_E_IO, "cannot open database %s", path.c_str());
 	char magic[8];
 	int64_t hdr[4];
-	if (fread(magic, 1, 8, f) != 8 || memcmp(magic, kMagic, 8) != 0 || fread(hdr, sizeof hdr, 1, f) != 1) {
-		fclose(f);
+	if (fread(magic, 1, 8, f) != 8 || memcmp(magic, kMagic, 8) != 0 || fread(hdr, sizeof hdr, 1, f) != 1)
 		return fail(PGX_E_FORMAT, "%s is not a pgxdb file", path.c_str());
-	}
 	// the header is checked against the file before anything is sized by it (a damaged file used to end in bad_alloc)
 	struct stat sb;
 	const bool have_size = fstat(fileno(f), &sb) == 0;
 	const int64_t n_seq = hdr[0], n_bases = hdr[1], n_words = hdr[3];
 	const bool sane = n_seq >= 0 && n_bases >= 0 && n_bases < (1ll << 32) - 64 && n_seq <= n_bases + 1 && n_words == (n_bases + 31) / 32 &&
 			  (!have_size || (int64_t)sb.st_size >= 40 + 4 * (n_seq + 1) + 8 * n_words * (hdr[2] ? 2 : 1) + 4 * n_seq);
-	if (!sane) {
-		fclose(f);
+	if (!sane)
 		return fail(PGX_E_FORMAT, "%s: header does not fit the file (%lld sequences, %lld bases, %lld words)", path.c_str(),
 			    (long long)n_seq, (long long)n_bases, (long long)n_words);
-	}
-	pgx_db *db = new pgx_db();
+	std::unique_ptr<pgx_db> db(new pgx_db());
 	db->n_seq = hdr[0];
 	db->n_bases = hdr[1];
 	db->has_amb = hdr[2] != 0;
@@ -671,12 +667,9 @@ static int db_read_file(const char *prefix, pgx_db **out)
 		ok = ok && (l == 0 || fread(&id[0], 1, l, f) == l);
 		db->ids.push_back(id);
 	}
-	fclose(f);
-	if (!ok) {
-		delete db;
+	if (!ok)
 		return fail(PGX_E_FORMAT, "%s is truncated", path.c_str());
-	}
-	*out = db;
+	out = std::move(db);
 	return 0;
 }
 
@@ -1235,9 +1228,9 @@ static int reads_build_pieces(pgx_reads *rd, const unsigned char *d_letters, con
 }
 
 int reads_from_fasta_ex(const char *path, int64_t first, int64_t count, bool fold_to_g, std::vector<uint32_t> *amb_count,
-			pgx_reads **out)
+			std::unique_ptr<pgx_reads> &out)
 {
-	if (!path || !out)
+	if (!path)
 		return fail(PGX_E_ARG, "pgx_reads_from_fasta: null argument");
 	PGX_TRY(require_device());
 	const bool trace = getenv("PGX_TRACE") != nullptr;
@@ -1257,7 +1250,7 @@ int reads_from_fasta_ex(const char *path, int64_t first, int64_t count, bool fol
 
 // the same for FASTA text already in memory (pgx_blastn_run streams large query files through this in pieces)
 int reads_from_fasta_text(std::shared_ptr<const TextBlob> text_ptr, int64_t first, int64_t count, bool fold_to_g,
-			  std::vector<uint32_t> *amb_count, pgx_reads **out)
+			  std::vector<uint32_t> *amb_count, std::unique_ptr<pgx_reads> &out)
 {
 	const TextBlob &text = *text_ptr;
 	PGX_TRY(require_device());
@@ -1270,15 +1263,11 @@ int reads_from_fasta_text(std::shared_ptr<const TextBlob> text_ptr, int64_t firs
 	// records, letters and names: found on the device for files under 4 GiB, by the host splitter otherwise
 	DeviceFasta df;
 	std::vector<uint64_t> rec_off; // n_rec + 1 letter offsets
-	pgx_reads *rd = new pgx_reads();
+	std::unique_ptr<pgx_reads> rd(new pgx_reads());
 	FastaLetters fl;
 	const bool on_device = text.size() < (1ull << 32) - 2;
 	if (on_device) {
-		int rc0 = fasta_split_device(text.data(), text.size(), df);
-		if (rc0 < 0) {
-			delete rd;
-			return rc0;
-		}
+		PGX_TRY(fasta_split_device(text.data(), text.size(), df));
 		rec_off.assign(df.let_off.begin(), df.let_off.end());
 	} else {
 		split_fasta_text(std::string(text.data(), text.size()), fl); // (4 GiB and more: the host splitter works on a string)
@@ -1326,93 +1315,83 @@ int reads_from_fasta_text(std::shared_ptr<const TextBlob> text_ptr, int64_t firs
 	for (int64_t i = 0; i <= count; i++)
 		loff[(size_t)i] = rec_off[(size_t)(first + i)] - l0;
 	DevBuf<unsigned char> d_letters_host;
-	int rc = 0;
 	const unsigned char *d_letters_ptr = nullptr;
 	if (on_device) {
 		d_letters_ptr = df.d_letters.data() + l0;
 		// the batch's own copy of its names (host and device); the file's text is let go when this call returns
 		const uint32_t nb0 = df.name_at[(size_t)first], nb1 = df.name_at[(size_t)(first + count)];
 		rd->h_text = std::make_shared<const TextBlob>(df.names.substr(nb0, nb1 - nb0));
-		rc = rd->d_names.alloc(nb1 - nb0 ? nb1 - nb0 : 1, 0, 16);
-		if (rc == 0 && nb1 > nb0 && hipMemcpy(rd->d_names.data(), df.d_names.data() + nb0, nb1 - nb0, hipMemcpyDeviceToDevice) != hipSuccess)
-			rc = fail(PGX_E_NODEVICE, "copy of the read names failed");
+		PGX_TRY(rd->d_names.alloc(nb1 - nb0 ? nb1 - nb0 : 1, 0, 16));
+		if (nb1 > nb0 && hipMemcpy(rd->d_names.data(), df.d_names.data() + nb0, nb1 - nb0, hipMemcpyDeviceToDevice) != hipSuccess)
+			return fail(PGX_E_NODEVICE, "copy of the read names failed");
 	} else {
 		rd->h_text = std::make_shared<const TextBlob>(std::move(own_names));
-		rc = rd->d_names.alloc(rd->h_text->size() ? rd->h_text->size() : 1, 0, 16);
-		if (rc == 0) rc = rd->d_names.upload((const unsigned char *)rd->h_text->data(), rd->h_text->size());
-		rc = d_letters_host.alloc(l1 - l0 ? l1 - l0 : 1, 0, 16);
-		if (rc == 0) rc = d_letters_host.upload((const unsigned char *)fl.letters.data() + l0, l1 - l0);
+		PGX_TRY(rd->d_names.alloc(rd->h_text->size() ? rd->h_text->size() : 1, 0, 16));
+		PGX_TRY(rd->d_names.upload((const unsigned char *)rd->h_text->data(), rd->h_text->size()));
+		PGX_TRY(d_letters_host.alloc(l1 - l0 ? l1 - l0 : 1, 0, 16));
+		PGX_TRY(d_letters_host.upload((const unsigned char *)fl.letters.data() + l0, l1 - l0));
 		d_letters_ptr = d_letters_host.data();
 	}
-	if (rc == 0) {
-		std::vector<uint32_t> at((size_t)count + 1, 0);
-		for (int64_t i = 0; i < count; i++)
-			at[(size_t)i + 1] = at[(size_t)i] + rd->name_len[(size_t)i];
-		rc = rd->d_name_at.alloc((size_t)count + 1);
-		if (rc == 0) rc = rd->d_name_at.upload(at.data(), at.size());
-	}
+	std::vector<uint32_t> at((size_t)count + 1, 0);
+	for (int64_t i = 0; i < count; i++)
+		at[(size_t)i + 1] = at[(size_t)i] + rd->name_len[(size_t)i];
+	PGX_TRY(rd->d_name_at.assign(at));
 	DevBuf<uint64_t> d_loff;
 	DevBuf<uint32_t> d_namb;
 	DevBuf<unsigned int> d_flag;
-	if (rc == 0) rc = d_loff.alloc((size_t)count + 1);
-	if (rc == 0) rc = d_loff.upload(loff.data(), loff.size());
-	if (rc == 0) rc = d_namb.alloc(count ? (size_t)count : 1);
-	if (rc == 0) rc = d_flag.alloc(1, 0, 0, true);
-	if (rc == 0) rc = rd->d_woff.alloc((size_t)count + 1);
-	if (rc == 0) rc = rd->d_woff.upload(rd->h_woff.data(), (size_t)count + 1);
-	if (rc == 0) rc = rd->d_fwd.alloc((size_t)nw + 24, 0, 0, true);
-	if (rc == 0 && !fold_to_g) rc = rd->d_fwd_amb.alloc((size_t)nw + 24, 0, 0, true);
-	if (rc == 0 && count > 0) {
+	PGX_TRY(d_loff.assign(loff));
+	PGX_TRY(d_namb.alloc(count ? (size_t)count : 1));
+	PGX_TRY(d_flag.alloc(1, 0, 0, true));
+	PGX_TRY(rd->d_woff.assign(rd->h_woff));
+	PGX_TRY(rd->d_fwd.alloc((size_t)nw + 24, 0, 0, true));
+	if (!fold_to_g)
+		PGX_TRY(rd->d_fwd_amb.alloc((size_t)nw + 24, 0, 0, true));
+	if (count > 0) {
 		hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, 0, d_letters_ptr, d_loff.data(),
 				   rd->d_woff.data(), (uint64_t)count, fold_to_g ? 1 : 0, rd->d_fwd.data(),
 				   fold_to_g ? (uint64_t *)nullptr : rd->d_fwd_amb.data(), d_namb.data(), d_flag.data());
 		if (hipGetLastError() != hipSuccess)
-			rc = fail(PGX_E_NODEVICE, "k_pack_reads launch failed");
+			return fail(PGX_E_NODEVICE, "k_pack_reads launch failed");
 	}
 	unsigned int flag = 0;
-	if (rc == 0) rc = d_flag.download(&flag, 1);
+	PGX_TRY(d_flag.download(&flag, 1));
 	rd->has_amb = flag != 0 && !fold_to_g;
-	if (rc == 0 && !rd->has_amb)
+	if (!rd->has_amb) {
 		rd->d_fwd_amb.release();
-	if (rc == 0 && rd->has_amb) {
+	} else {
 		// which reads carry an ambiguity letter: the search sends only those through the ambiguity-aware kernels
 		std::vector<uint32_t> na((size_t)count);
-		rc = d_namb.download(na.data(), (size_t)count);
+		PGX_TRY(d_namb.download(na.data(), (size_t)count));
 		rd->h_read_amb.resize((size_t)count);
 		for (int64_t i = 0; i < count; i++)
 			rd->h_read_amb[(size_t)i] = na[(size_t)i] != 0;
 	}
-	if (rc == 0 && amb_count) {
+	if (amb_count) {
 		amb_count->assign((size_t)count, 0);
-		rc = d_namb.download(amb_count->data(), (size_t)count);
+		PGX_TRY(d_namb.download(amb_count->data(), (size_t)count));
 	}
-	if (rc == 0 && fold_to_g) {
+	if (fold_to_g) {
 		// SOAP row formatting echoes the read as aligned: keep a host copy of the packed forward strand
 		rd->h_fwd.assign(nw + 2, 0);
-		rc = rd->d_fwd.download(rd->h_fwd.data(), (size_t)nw);
+		PGX_TRY(rd->d_fwd.download(rd->h_fwd.data(), (size_t)nw));
 	}
-	if (rc == 0 && rd->has_amb && getenv("PGX_NO_PIECES") == nullptr)
-		rc = reads_build_pieces(rd, d_letters_ptr, d_loff.data(), d_namb.data());
+	if (rd->has_amb && getenv("PGX_NO_PIECES") == nullptr)
+		PGX_TRY(reads_build_pieces(rd.get(), d_letters_ptr, d_loff.data(), d_namb.data()));
 	const auto t_pack = now();
-	if (rc == 0)
-		rc = reads_finish(rd);
-	if (rc < 0) {
-		delete rd;
-		return rc;
-	}
+	PGX_TRY(reads_finish(rd.get()));
 	if (trace) {
 		(void)hipDeviceSynchronize();
 		fprintf(stderr, "[pgx trace] reads_from_fasta: split %.1f ms, tables+pack %.1f ms, strands %.1f ms\n", ms(t_read, t_split),
 			ms(t_split, t_pack), ms(t_pack, now()));
 	}
-	*out = rd;
+	out = std::move(rd);
 	return 0;
 }
 
 // a database whose ambiguity codes read as G (SOAP mode), built from a file database
-int db_fold_amb_to_g(const pgx_db *src, pgx_db **out)
+int db_fold_amb_to_g(const pgx_db *src, std::unique_ptr<pgx_db> &out)
 {
-	pgx_db *db = new pgx_db();
+	std::unique_ptr<pgx_db> db(new pgx_db());
 	db->n_seq = src->n_seq;
 	db->n_bases = src->n_bases;
 	db->has_amb = false;
@@ -1422,16 +1401,12 @@ int db_fold_amb_to_g(const pgx_db *src, pgx_db **out)
 	if (src->has_amb)
 		for (size_t w = 0; w < db->h_words.size() && w < src->h_amb.size(); w++)
 			db->h_words[w] |= src->h_amb[w] << 1; // flagged bases hold code 0: setting the high bit makes them G
-	int rc = db_upload_and_index(db);
-	if (rc < 0) {
-		delete db;
-		return rc;
-	}
-	*out = db;
+	PGX_TRY(db_upload_and_index(db.get()));
+	out = std::move(db);
 	return 0;
 }
 
-int db_read_host(const char *prefix, pgx_db **out) { return db_read_file(prefix, out); }
+int db_read_host(const char *prefix, std::unique_ptr<pgx_db> &out) { return db_read_file(prefix, out); }
 
 // number of FASTA records of a file (lines starting with '>'), without packing anything
 // records (lines that start with '>') in a piece of FASTA text; `at_line_start` carries over between pieces
@@ -1507,11 +1482,7 @@ int pgx_db_build(const char *fasta_path, const char *prefix)
 		return fail(PGX_E_IO, "cannot open FASTA file %s", fasta_path);
 	PackedSet ps;
 	pack_fasta_text(text, ps);
-	pgx_db *db = nullptr;
-	db_from_packed(ps, &db);
-	int rc = db_write_file(db, prefix);
-	delete db;
-	return rc;
+	return db_write_file(db_from_packed(ps).get(), prefix);
 }
 
 int pgx_db_open(const char *prefix, pgx_db **out)
@@ -1520,14 +1491,10 @@ int pgx_db_open(const char *prefix, pgx_db **out)
 		return fail(PGX_E_ARG, "pgx_db_open: null argument");
 	PGX_TRY(require_device());
 	return pgx::guard("pgx_db_open", [&]() -> int {
-		pgx_db *db = nullptr;
-		PGX_TRY(db_read_file(prefix, &db));
-		int rc = db_upload_and_index(db);
-		if (rc < 0) {
-			delete db;
-			return rc;
-		}
-		*out = db;
+		std::unique_ptr<pgx_db> db;
+		PGX_TRY(db_read_file(prefix, db));
+		PGX_TRY(db_upload_and_index(db.get()));
+		*out = db.release();
 		return 0;
 	});
 }
@@ -1543,14 +1510,9 @@ int pgx_db_from_fasta(const char *fasta_path, pgx_db **out)
 		return fail(PGX_E_IO, "cannot open FASTA file %s", fasta_path);
 	PackedSet ps;
 	pack_fasta_text(text, ps);
-	pgx_db *db = nullptr;
-	db_from_packed(ps, &db);
-	int rc = db_upload_and_index(db);
-	if (rc < 0) {
-		delete db;
-		return rc;
-	}
-	*out = db;
+	std::unique_ptr<pgx_db> db = db_from_packed(ps);
+	PGX_TRY(db_upload_and_index(db.get()));
+	*out = db.release();
 	return 0;
 }
 
@@ -1579,36 +1541,26 @@ int pgx_db_from_synth(const pgx_synth_cfg *cfg, pgx_db **out)
 	if (!cfg || !out || cfg->n_seq <= 0 || cfg->seq_len <= 0 || cfg->n_genus <= 0)
 		return fail(PGX_E_ARG, "pgx_db_from_synth: bad configuration");
 	PGX_TRY(require_device());
-	pgx_db *db = new pgx_db();
+	std::unique_ptr<pgx_db> db(new pgx_db());
 	db->n_seq = cfg->n_seq;
 	db->n_bases = cfg->n_seq * (int64_t)cfg->seq_len;
-	if (db->n_bases >= (1ll << 32) - 64) {
-		delete db;
+	if (db->n_bases >= (1ll << 32) - 64)
 		return fail(PGX_E_LIMIT, "synthetic database exceeds the 32-bit position limit");
-	}
 	db->h_seq_off.resize((size_t)db->n_seq + 1);
 	for (int64_t i = 0; i <= db->n_seq; i++)
 		db->h_seq_off[(size_t)i] = (uint32_t)(i * cfg->seq_len);
 	db->synthetic_ids = true;
-	synth_ids(db);
+	synth_ids(db.get());
 	size_t nw = ((size_t)db->n_bases + 31) / 32;
-	int rc = db->d_words.alloc(nw, 24, 24, true);
-	if (rc == 0) {
-		hipLaunchKernelGGL(k_synth_db, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, 0, cfg->seed,
-				   (uint64_t)cfg->n_seq, (uint32_t)cfg->seq_len, (uint64_t)cfg->n_genus,
-				   db->d_words.data(), (uint64_t)nw, (uint64_t)db->n_bases);
-		if (hipGetLastError() != hipSuccess)
-			rc = fail(PGX_E_NODEVICE, "k_synth_db launch failed");
-	}
-	if (rc == 0)
-		rc = db_upload_offsets(db);
-	if (rc == 0)
-		rc = db_build_index(db);
-	if (rc < 0) {
-		delete db;
-		return rc;
-	}
-	*out = db;
+	PGX_TRY(db->d_words.alloc(nw, 24, 24, true));
+	hipLaunchKernelGGL(k_synth_db, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, 0, cfg->seed,
+			   (uint64_t)cfg->n_seq, (uint32_t)cfg->seq_len, (uint64_t)cfg->n_genus,
+			   db->d_words.data(), (uint64_t)nw, (uint64_t)db->n_bases);
+	if (hipGetLastError() != hipSuccess)
+		return fail(PGX_E_NODEVICE, "k_synth_db launch failed");
+	PGX_TRY(db_upload_offsets(db.get()));
+	PGX_TRY(db_build_index(db.get()));
+	*out = db.release();
 	return 0;
 }
 
@@ -1617,51 +1569,55 @@ int pgx_reads_from_synth(const pgx_synth_cfg *cfg, int64_t first, int64_t count,
 	if (!cfg || !out || count < 0 || cfg->read_len <= 0 || cfg->read_len > cfg->seq_len)
 		return fail(PGX_E_ARG, "pgx_reads_from_synth: bad configuration");
 	PGX_TRY(require_device());
-	pgx_reads *rd = new pgx_reads();
-	rd->n = count;
-	rd->first = first;
-	rd->synthetic = true;
 	uint32_t wpr = ((uint32_t)cfg->read_len + 31) / 32;
 	// (equal reads: a fixed stride with the property of place_read_words)
 	const uint32_t stride = wpr <= 1 ? 1 : wpr <= 2 ? 2 : wpr <= 4 ? 4 : (wpr + 7u) & ~7u;
 	if ((uint64_t)count * stride >= 0xFFFFFFFFull)
 		return fail(PGX_E_LIMIT, "pgx_reads_from_synth: more than 2^32 words in one batch");
+	std::unique_ptr<pgx_reads> rd(new pgx_reads());
+	rd->n = count;
+	rd->first = first;
+	rd->synthetic = true;
 	rd->n_words = count * (int64_t)stride;
 	rd->max_len = cfg->read_len;
 	rd->h_len.assign((size_t)count, (uint32_t)cfg->read_len);
 	rd->h_woff.resize((size_t)count + 1);
 	for (int64_t i = 0; i <= count; i++)
 		rd->h_woff[(size_t)i] = (uint32_t)(i * stride);
-	int rc = rd->d_fwd.alloc((size_t)rd->n_words + 24, 0, 0, true);
-	if (rc == 0 && count > 0) {
+	PGX_TRY(rd->d_fwd.alloc((size_t)rd->n_words + 24, 0, 0, true));
+	if (count > 0) {
 		uint64_t nt = (uint64_t)count * wpr;
 		hipLaunchKernelGGL(k_synth_reads, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, 0, cfg->seed,
 				   (uint64_t)cfg->n_seq, (uint32_t)cfg->seq_len, (uint64_t)cfg->n_genus, cfg->read_seed,
 				   (uint32_t)cfg->read_len, (uint64_t)first, (uint64_t)count, wpr, stride, rd->d_fwd.data());
 		if (hipGetLastError() != hipSuccess)
-			rc = fail(PGX_E_NODEVICE, "k_synth_reads launch failed");
+			return fail(PGX_E_NODEVICE, "k_synth_reads launch failed");
 	}
-	if (rc == 0)
-		rc = reads_finish(rd);
-	if (rc < 0) {
-		delete rd;
-		return rc;
-	}
+	PGX_TRY(reads_finish(rd.get()));
 	trace_point("reads_from_synth");
-	*out = rd;
+	*out = rd.release();
 	return 0;
 }
 
 int pgx_reads_from_fasta(const char *path, int64_t first, int64_t count, pgx_reads **out)
 {
-	return pgx::reads_from_fasta_ex(path, first, count, false, nullptr, out);
+	if (!out)
+		return fail(PGX_E_ARG, "pgx_reads_from_fasta: null argument");
+	std::unique_ptr<pgx_reads> rd;
+	PGX_TRY(pgx::reads_from_fasta_ex(path, first, count, false, nullptr, rd));
+	*out = rd.release();
+	return 0;
 }
 
 int pgx_reads_from_fasta_text(const char *text, size_t len, int64_t first, int64_t count, pgx_reads **out)
 {
 	if ((!text && len) || !out)
 		return fail(PGX_E_ARG, "pgx_reads_from_fasta_text: null argument");
-	return pgx::reads_from_fasta_text(std::make_shared<const pgx::TextBlob>(std::string(text ? text : "", len)), first, count, false, nullptr, out);
+	std::unique_ptr<pgx_reads> rd;
+	PGX_TRY(pgx::reads_from_fasta_text(std::make_shared<const pgx::TextBlob>(std::string(text ? text : "", len)), first, count, false,
+					   nullptr, rd));
+	*out = rd.release();
+	return 0;
 }
 
 // A batch back as FASTA text (">name" + one sequence line per read): the hand-over file between Trim and Classify
@@ -1813,7 +1769,7 @@ int pgx_db_alloc_like(const pgx_db_shape *s, pgx_db **out)
 	if (!s || !out)
 		return fail(PGX_E_ARG, "pgx_db_alloc_like: null argument");
 	PGX_TRY(require_device());
-	pgx_db *db = new pgx_db();
+	std::unique_ptr<pgx_db> db(new pgx_db());
 	db->n_seq = s->n_seq;
 	db->n_bases = s->n_bases;
 	db->has_amb = s->has_amb != 0;
@@ -1821,26 +1777,17 @@ int pgx_db_alloc_like(const pgx_db_shape *s, pgx_db **out)
 	db->n_postings = s->n_postings;
 	db->synthetic_ids = s->synthetic_ids != 0;
 	size_t nw = ((size_t)db->n_bases + 31) / 32;
-	int rc = db->d_words.alloc(nw, 24, 24, true);
-	if (rc == 0 && db->has_amb)
-		rc = db->d_amb.alloc(nw, 24, 24, true);
-	if (rc == 0)
-		rc = db->d_seq_off.alloc((size_t)db->n_seq + 1);
+	PGX_TRY(db->d_words.alloc(nw, 24, 24, true));
+	if (db->has_amb)
+		PGX_TRY(db->d_amb.alloc(nw, 24, 24, true));
+	PGX_TRY(db->d_seq_off.alloc((size_t)db->n_seq + 1));
 	if (bcast_whole_index()) {
-		if (rc == 0)
-			rc = db->d_blk_subj.alloc(((size_t)db->n_bases >> kBlkShift) + 2);
-		if (rc == 0)
-			rc = db->d_bucket_off.alloc((1ull << db->index_bits) + 1);
-		if (rc == 0)
-			rc = db->d_postings.alloc(db->n_postings ? (size_t)db->n_postings : 1);
-		if (rc == 0)
-			rc = db->d_post_ctx.alloc(db->n_postings ? (size_t)db->n_postings : 1);
+		PGX_TRY(db->d_blk_subj.alloc(((size_t)db->n_bases >> kBlkShift) + 2));
+		PGX_TRY(db->d_bucket_off.alloc((1ull << db->index_bits) + 1));
+		PGX_TRY(db->d_postings.alloc(db->n_postings ? (size_t)db->n_postings : 1));
+		PGX_TRY(db->d_post_ctx.alloc(db->n_postings ? (size_t)db->n_postings : 1));
 	}
-	if (rc < 0) {
-		delete db;
-		return rc;
-	}
-	*out = db;
+	*out = db.release();
 	return 0;
 }
 

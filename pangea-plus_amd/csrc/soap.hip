@@ -467,16 +467,15 @@ namespace pgx {
 
 // the reference as the ELF's index sees it: ambiguity codes folded to G, the segments between runs of >= 10 of them
 struct SoapDb {
-	pgx_db *db = nullptr;
+	std::unique_ptr<pgx_db> db;
 	DevBuf<uint32_t> d_seg_lo, d_seg_hi;
 	SoapView v{};
-	~SoapDb() { pgx_db_close(db); }
 };
 
 static int soap_db_open(const char *prefix, SoapDb &sd)
 {
-	pgx_db *src = nullptr;
-	PGX_TRY(db_read_host(prefix, &src));
+	std::unique_ptr<pgx_db> src;
+	PGX_TRY(db_read_host(prefix, src));
 	// segments between runs of >= 10 ambiguity codes (what 2bwt-builder cuts out)
 	std::vector<uint32_t> seg_lo, seg_hi;
 	for (int64_t s = 0; s < src->n_seq; s++) {
@@ -497,15 +496,11 @@ static int soap_db_open(const char *prefix, SoapDb &sd)
 			k = r > k ? r : k + 1;
 		}
 	}
-	int rc = db_fold_amb_to_g(src, &sd.db);
-	delete src;
-	if (rc < 0)
-		return rc;
-	PGX_TRY(sd.d_seg_lo.alloc(seg_lo.size() ? seg_lo.size() : 1));
-	PGX_TRY(sd.d_seg_lo.upload(seg_lo.data(), seg_lo.size()));
-	PGX_TRY(sd.d_seg_hi.alloc(seg_hi.size() ? seg_hi.size() : 1));
-	PGX_TRY(sd.d_seg_hi.upload(seg_hi.data(), seg_hi.size()));
-	const pgx_db *db = sd.db;
+	PGX_TRY(db_fold_amb_to_g(src.get(), sd.db));
+	src.reset();
+	PGX_TRY(sd.d_seg_lo.assign(seg_lo));
+	PGX_TRY(sd.d_seg_hi.assign(seg_hi));
+	const pgx_db *db = sd.db.get();
 	sd.v.words = db->d_words.data();
 	sd.v.seq_off = db->d_seq_off.data();
 	sd.v.blk_subj = db->d_blk_subj.data();
@@ -520,7 +515,7 @@ static int soap_db_open(const char *prefix, SoapDb &sd)
 
 // one file of reads searched: the rows of read r are hits[first[r] .. first[r] + n_best[r]), in (subject, position, strand) order
 struct SoapSearch {
-	pgx_reads *rd = nullptr;
+	std::unique_ptr<pgx_reads> rd;
 	std::vector<uint32_t> nn, best, n_best;
 	std::vector<unsigned long long> first;
 	std::vector<SoapHit> hits;
@@ -528,7 +523,6 @@ struct SoapSearch {
 	DevBuf<uint32_t> d_best, d_nbest;
 	DevBuf<unsigned long long> d_first;
 	std::vector<int> fw, rv; // bases of the read last unpacked
-	~SoapSearch() { pgx_reads_close(rd); }
 	void unpack(size_t r)
 	{
 		const int L = (int)rd->h_len[r];
@@ -551,7 +545,7 @@ struct SoapSearch {
 // seed_len > 0: seed mode (pgx_soap_run_seeded), a read with no whole-read placement is placed by its seed
 static int soap_search(const SoapDb &sd, const char *reads_path, int max_n, int mode, SoapSearch &s, int seed_len = 0, int rest_cap = 0)
 {
-	PGX_TRY(reads_from_fasta_ex(reads_path, 0, -1, true, &s.nn, &s.rd));
+	PGX_TRY(reads_from_fasta_ex(reads_path, 0, -1, true, &s.nn, s.rd));
 	const size_t n = (size_t)s.rd->n;
 	s.best.assign(n, 3);
 	s.n_best.assign(n, 0);
@@ -629,7 +623,7 @@ static int soap_run_single(const pgx_soap_opts *o, const SoapDb &sd, int seed_le
 			const uint32_t lim = o->repeat_mode == 2 ? nb : 1;
 			for (uint32_t x = 0; x < lim; x++)
 				soap_row(out, o->report_id ? std::to_string(r) : s.rd->name_of(r), // -t: the read's 0-based ordinal in the file
-					 ((h[x].strand_nmis >> 8) & 1) ? s.rv : s.fw, h[x], nb, sd.db, o->repeat_mode, 'a', false, seed_len);
+					 ((h[x].strand_nmis >> 8) & 1) ? s.rv : s.fw, h[x], nb, sd.db.get(), o->repeat_mode, 'a', false, seed_len);
 			printed = true;
 		}
 		if (!printed && (nb <= 1 || seed_len > 0))
@@ -709,9 +703,9 @@ static int soap_run_paired(const pgx_soap_opts *o, const SoapDb &sd)
 					if (o->repeat_mode != 2 && seen++ > 0)
 						continue;
 					if (mate == 0)
-						soap_row(out, a.rd->name_of(i), (ha[x].strand_nmis >> 8) ? a.rv : a.fw, ha[x], np, sd.db, o->repeat_mode, 'a', true);
+						soap_row(out, a.rd->name_of(i), (ha[x].strand_nmis >> 8) ? a.rv : a.fw, ha[x], np, sd.db.get(), o->repeat_mode, 'a', true);
 					else
-						soap_row(out, b.rd->name_of(i), (hb[y].strand_nmis >> 8) ? b.rv : b.fw, hb[y], np, sd.db, o->repeat_mode, 'b', true);
+						soap_row(out, b.rd->name_of(i), (hb[y].strand_nmis >> 8) ? b.rv : b.fw, hb[y], np, sd.db.get(), o->repeat_mode, 'b', true);
 				}
 		}
 		if (np > 0 && !ambiguous)
@@ -723,7 +717,7 @@ static int soap_run_paired(const pgx_soap_opts *o, const SoapDb &sd)
 			if (np == 0 && nh > 0 && !(o->repeat_mode == 0 && nh > 1)) {
 				const uint32_t lim = o->repeat_mode == 2 ? nh : 1;
 				for (uint32_t x = 0; x < lim; x++)
-					soap_row(un2, m.rd->name_of(i), (h[x].strand_nmis >> 8) ? m.rv : m.fw, h[x], nh, sd.db, o->repeat_mode, mate ? 'b' : 'a',
+					soap_row(un2, m.rd->name_of(i), (h[x].strand_nmis >> 8) ? m.rv : m.fw, h[x], nh, sd.db.get(), o->repeat_mode, mate ? 'b' : 'a',
 						 true);
 			} else {
 				m.unmapped(unm, i);

@@ -490,9 +490,9 @@ static bool slurp(const std::string &path, std::vector<uint8_t> &out)
 }
 
 // host part of open: usable without a device for the single lookups of the CLI
-static pgx_taxdb *tax_load(const char *dir)
+static std::unique_ptr<pgx_taxdb> tax_load(const char *dir)
 {
-	pgx_taxdb *db = new pgx_taxdb();
+	std::unique_ptr<pgx_taxdb> db(new pgx_taxdb());
 	std::vector<uint8_t> raw;
 	if (slurp(join_path(dir, "gi_taxid_nucl.dmp.bin"), raw)) {
 		db->have_gi = true;
@@ -516,11 +516,9 @@ int pgx_tax_open(const char *dir, pgx_taxdb **out)
 	if (!dir || !out)
 		return fail(PGX_E_ARG, "pgx_tax_open: null argument");
 	PGX_TRY(require_device());
-	pgx_taxdb *db = tax_load(dir);
-	if (!db->have_gi || !db->have_nodes || !db->have_names) {
-		delete db;
+	std::unique_ptr<pgx_taxdb> db = tax_load(dir);
+	if (!db->have_gi || !db->have_nodes || !db->have_names)
 		return fail(PGX_E_IO, "taxonomy binaries missing in %s (run tax_class -c)", dir);
-	}
 	std::vector<int32_t> tid(db->n_nodes), par(db->n_nodes);
 	std::vector<int8_t> code(db->n_nodes);
 	for (size_t i = 0; i < db->n_nodes; i++) {
@@ -529,26 +527,11 @@ int pgx_tax_open(const char *dir, pgx_taxdb **out)
 		par[i] = rd32(r + 4);
 		code[i] = driver_rank_code((int8_t)r[8]);
 	}
-	int rc = db->d_gi2tax.alloc(db->gi2tax.size());
-	if (rc == 0)
-		rc = db->d_gi2tax.upload(db->gi2tax.data(), db->gi2tax.size());
-	if (rc == 0)
-		rc = db->d_node_taxid.alloc(db->n_nodes);
-	if (rc == 0)
-		rc = db->d_node_taxid.upload(tid.data(), tid.size());
-	if (rc == 0)
-		rc = db->d_node_parent.alloc(db->n_nodes);
-	if (rc == 0)
-		rc = db->d_node_parent.upload(par.data(), par.size());
-	if (rc == 0)
-		rc = db->d_node_code.alloc(db->n_nodes);
-	if (rc == 0)
-		rc = db->d_node_code.upload(code.data(), code.size());
-	if (rc < 0) {
-		delete db;
-		return rc;
-	}
-	*out = db;
+	PGX_TRY(db->d_gi2tax.assign(db->gi2tax));
+	PGX_TRY(db->d_node_taxid.assign(tid));
+	PGX_TRY(db->d_node_parent.assign(par));
+	PGX_TRY(db->d_node_code.assign(code));
+	*out = db.release();
 	return 0;
 }
 
@@ -632,7 +615,6 @@ int pgx_tax_cli(int argc, char **argv, const char *dir, char **out_text, char **
 					 "   -v --verbose           turn on verbose output\n"
 					 "   -h --help              print this help message\n";
 	Text out, err;
-	int status = 0;
 	char verb = 0;
 	int index = 0, tax_id = 0, verbose = 0, c;
 	bool helped = false;
@@ -649,93 +631,94 @@ int pgx_tax_cli(int argc, char **argv, const char *dir, char **out_text, char **
 		default: helped = true; break;
 		}
 	}
-	auto finish = [&](int st) {
-		if (out_text)
-			*out_text = out.release_malloc(nullptr);
-		if (err_text)
-			*err_text = err.release_malloc(nullptr);
-		return st;
-	};
-	if (helped) {
-		out.s += kHelp;
-		return finish(0);
-	}
-	if (verbose)
-		out.s += "verbose flag is set\n";
-	if (verb == 'c') {
-		pgx_tax_create(dir);
-		return finish(0);
-	}
-	if (!verb) {
-		out.s += kHelp;
-		return finish(0);
-	}
-	pgx_taxdb *db = tax_load(dir);
-	auto lookup_failed = [&](int rc) {
-		err.s += rc == -1 ? "fopen: No such file or directory\n" : "fseek: Invalid argument\n";
-		out.s += "Error.\n";
-		status = 255;
-	};
-	pgx_node node;
-	if (verb == 's' || verb == 'g') {
-		int rc = !db->have_gi ? -1 : ((long)index - 1 < 0 ? -2 : 0);
-		if (rc < 0) {
-			lookup_failed(rc);
-		} else {
-			tax_id = (size_t)index - 1 < db->gi2tax.size() ? db->gi2tax[(size_t)index - 1] : 0;
-			if (verbose)
-				out.printf("%d\t%d\n", index, tax_id);
-			if (tax_id == 0) {
-				out.s += "0\n";
-			} else if (verb == 'g') {
-				rc = tax_node_record(db, tax_id, &node);
-				if (rc < 0) {
-					lookup_failed(rc);
-				} else {
-					if (verbose)
-						out.printf("%d\n", node.tax_id);
-					format_node_text(&node, out);
-				}
+	auto body = [&]() -> int {
+		if (helped) {
+			out.s += kHelp;
+			return 0;
+		}
+		if (verbose)
+			out.s += "verbose flag is set\n";
+		if (verb == 'c') {
+			pgx_tax_create(dir);
+			return 0;
+		}
+		if (!verb) {
+			out.s += kHelp;
+			return 0;
+		}
+		const std::unique_ptr<pgx_taxdb> db = tax_load(dir);
+		int status = 0;
+		auto lookup_failed = [&](int rc) {
+			err.s += rc == -1 ? "fopen: No such file or directory\n" : "fseek: Invalid argument\n";
+			out.s += "Error.\n";
+			status = 255;
+		};
+		pgx_node node;
+		if (verb == 's' || verb == 'g') {
+			int rc = !db->have_gi ? -1 : ((long)index - 1 < 0 ? -2 : 0);
+			if (rc < 0) {
+				lookup_failed(rc);
 			} else {
-				while (tax_id != 1) {
-					rc = tax_node_record(db, tax_id, &node);
+				tax_id = (size_t)index - 1 < db->gi2tax.size() ? db->gi2tax[(size_t)index - 1] : 0;
+				if (verbose)
+					out.printf("%d\t%d\n", index, tax_id);
+				if (tax_id == 0) {
+					out.s += "0\n";
+				} else if (verb == 'g') {
+					rc = tax_node_record(db.get(), tax_id, &node);
 					if (rc < 0) {
 						lookup_failed(rc);
-						break;
-					}
-					if (verbose)
-						out.printf("%d\n", node.tax_id);
-					tax_id = node.parent_tax_id;
-					if (tax_id != 1)
+					} else {
+						if (verbose)
+							out.printf("%d\n", node.tax_id);
 						format_node_text(&node, out);
+					}
+				} else {
+					while (tax_id != 1) {
+						rc = tax_node_record(db.get(), tax_id, &node);
+						if (rc < 0) {
+							lookup_failed(rc);
+							break;
+						}
+						if (verbose)
+							out.printf("%d\n", node.tax_id);
+						tax_id = node.parent_tax_id;
+						if (tax_id != 1)
+							format_node_text(&node, out);
+					}
 				}
 			}
+		} else if (verb == 't') {
+			int rc = tax_node_record(db.get(), tax_id, &node);
+			if (rc < 0) {
+				lookup_failed(rc);
+			} else {
+				if (verbose)
+					out.printf("%d\n", node.tax_id);
+				format_node_text(&node, out);
+			}
+		} else if (verb == 'n') {
+			std::vector<const uint8_t *> recs;
+			int failed_seeks = 0;
+			const int found = tax_names_lookup(db.get(), tax_id, recs, &failed_seeks);
+			for (int k = 0; k < failed_seeks; k++)
+				err.s += k == 0 ? "fseek: Invalid argument\n" : "fseek: Bad file descriptor\n";
+			if (found < 0)
+				lookup_failed(-1);
+			else if (found == 0)
+				out.s += "0\n";
+			else
+				for (const uint8_t *r : recs)
+					format_name_text(r, out);
 		}
-	} else if (verb == 't') {
-		int rc = tax_node_record(db, tax_id, &node);
-		if (rc < 0) {
-			lookup_failed(rc);
-		} else {
-			if (verbose)
-				out.printf("%d\n", node.tax_id);
-			format_node_text(&node, out);
-		}
-	} else if (verb == 'n') {
-		std::vector<const uint8_t *> recs;
-		int failed_seeks = 0;
-		int rc = tax_names_lookup(db, tax_id, recs, &failed_seeks);
-		for (int k = 0; k < failed_seeks; k++)
-			err.s += k == 0 ? "fseek: Invalid argument\n" : "fseek: Bad file descriptor\n";
-		if (rc < 0)
-			lookup_failed(-1);
-		else if (rc == 0)
-			out.s += "0\n";
-		else
-			for (const uint8_t *r : recs)
-				format_name_text(r, out);
-	}
-	delete db;
-	return finish(status);
+		return status;
+	};
+	const int status = body();
+	if (out_text)
+		*out_text = out.release_malloc(nullptr);
+	if (err_text)
+		*err_text = err.release_malloc(nullptr);
+	return status;
 }
 
 int pgx_tax_lineage_batch(pgx_taxdb *db, const int32_t *gi, int64_t n, int32_t *lineage, int32_t *count, int32_t *status)

@@ -953,103 +953,96 @@ extern "C" int pgx_trim_file(const pgx_trim_opts *o, char **log_text, char **fas
 	*mode = PGX_TRIM_NONE;
 	PGX_TRY(require_device());
 	Text log;
-	auto finish = [&](int rc) {
-		*log_text = log.release_malloc(nullptr);
-		return rc;
-	};
-	if (!perl_true(o->a)) { // :53
-		log.s += kTrimUsage;
-		return finish(0);
-	}
-	bool ok = false;
-	g_clock.tick("start");
-	const std::string a = read_text_file(o->a, &ok);
-	if (!ok) {
-		log.printf("Error: Unable to open %s.\n", o->a); // :68-71
-		return finish(0);
-	}
-	const bool paired = perl_true(o->b);
-	std::string b;
-	if (paired) {
-		b = read_text_file(o->b, &ok);
-		if (!ok) {
-			log.printf("Error: Unable to open %s.\n", o->b); // :78-81
-			return finish(0);
+	return with_text(log, log_text, [&]() -> int {
+		if (!perl_true(o->a)) { // :53
+			log.s += kTrimUsage;
+			return 0;
 		}
-	}
-	uint64_t gap = 189; // :36
-	long long t1 = 11, t2 = 10; // :35
-	if (perl_true(o->g)) { // :86-88; for ($r = 0; $r < $GAPSIZE; $r++)
-		const double g = perl_num(o->g, strlen(o->g));
-		gap = g > 0 ? (g > 2147483647.0 ? 2147483647ull : (uint64_t)std::ceil(g)) : 0;
-	}
-	if (perl_true(o->t)) { // :90-92
-		const double t = perl_num(o->t, strlen(o->t));
-		if (!(t > -1.0) || !(t < 2147483647.0))
-			return finish(fail(PGX_E_ARG, "-t %s: a negative truncate size is not covered", o->t));
-		t1 = (long long)t;
-		t2 = (long long)(t - 1.0);
-	}
-	int rc = 0;
-	g_clock.tick("read files");
-	if (!a.empty() && a[0] == '>') { // :117-143; RUNBLAST was opened before (:115) and stays empty unless -j writes to it
-		if (o->j) {
-			if (paired) {
-				*mode = PGX_TRIM_FASTA_JOIN;
-				long long jg = -1; // `if ($parameters{g})`: without -g no N's at all, $GAPSIZE is not consulted (:338)
-				if (perl_true(o->g)) {
-					const double g = perl_num(o->g, strlen(o->g));
-					jg = g > 0 ? (g > 2147483647.0 ? 2147483647ll : (long long)std::ceil(g)) : 0;
-				}
-				return finish(join_fasta_device(a, b, jg, fasta_text, fasta_len)); // exit: no closing message (:124)
+		bool ok = false;
+		g_clock.tick("start");
+		const std::string a = read_text_file(o->a, &ok);
+		if (!ok) {
+			log.printf("Error: Unable to open %s.\n", o->a); // :68-71
+			return 0;
+		}
+		const bool paired = perl_true(o->b);
+		std::string b;
+		if (paired) {
+			b = read_text_file(o->b, &ok);
+			if (!ok) {
+				log.printf("Error: Unable to open %s.\n", o->b); // :78-81
+				return 0;
 			}
-			log.s += "Error. Input is -j for joining ends, but you did not provided both sequence a and b with -a and -b options.\n\n";
+		}
+		uint64_t gap = 189; // :36
+		long long t1 = 11, t2 = 10; // :35
+		if (perl_true(o->g)) { // :86-88; for ($r = 0; $r < $GAPSIZE; $r++)
+			const double g = perl_num(o->g, strlen(o->g));
+			gap = g > 0 ? (g > 2147483647.0 ? 2147483647ull : (uint64_t)std::ceil(g)) : 0;
+		}
+		if (perl_true(o->t)) { // :90-92
+			const double t = perl_num(o->t, strlen(o->t));
+			if (!(t > -1.0) || !(t < 2147483647.0))
+				return fail(PGX_E_ARG, "-t %s: a negative truncate size is not covered", o->t);
+			t1 = (long long)t;
+			t2 = (long long)(t - 1.0);
+		}
+		g_clock.tick("read files");
+		if (!a.empty() && a[0] == '>') { // :117-143; RUNBLAST was opened before (:115) and stays empty unless -j writes to it
+			if (o->j) {
+				if (paired) {
+					*mode = PGX_TRIM_FASTA_JOIN;
+					long long jg = -1; // `if ($parameters{g})`: without -g no N's at all, $GAPSIZE is not consulted (:338)
+					if (perl_true(o->g)) {
+						const double g = perl_num(o->g, strlen(o->g));
+						jg = g > 0 ? (g > 2147483647.0 ? 2147483647ll : (long long)std::ceil(g)) : 0;
+					}
+					return join_fasta_device(a, b, jg, fasta_text, fasta_len); // exit: no closing message (:124)
+				}
+				log.s += "Error. Input is -j for joining ends, but you did not provided both sequence a and b with -a and -b options.\n\n";
+				*mode = PGX_TRIM_UNKNOWN;
+				*fasta_text = (char *)calloc(1, 1);
+				return 0;
+			}
 			*mode = PGX_TRIM_UNKNOWN;
 			*fasta_text = (char *)calloc(1, 1);
-			return finish(0);
+			if (!perl_true(o->q)) {
+				log.s += "Error: Please, specify the FASTA quality file with -q option.\n";
+				return 0;
+			}
+			log.printf("%s\n", o->q); // :129
+			const std::string q = read_text_file(o->q, &ok);
+			if (!ok) {
+				log.printf("Error: Unable to open %s required for FASTA file triming.\n", o->q);
+				return 0;
+			}
+			*mode = PGX_TRIM_FASTA_QUAL;
+			PGX_TRY(parse_fasta_device(a, q, log));
+			log.s += "Trimming complete.\n";
+			return 0;
 		}
-		*mode = PGX_TRIM_UNKNOWN;
-		*fasta_text = (char *)calloc(1, 1);
-		if (!perl_true(o->q)) {
-			log.s += "Error: Please, specify the FASTA quality file with -q option.\n";
-			return finish(0);
-		}
-		log.printf("%s\n", o->q); // :129
-		const std::string q = read_text_file(o->q, &ok);
-		if (!ok) {
-			log.printf("Error: Unable to open %s required for FASTA file triming.\n", o->q);
-			return finish(0);
-		}
-		*mode = PGX_TRIM_FASTA_QUAL;
-		rc = parse_fasta_device(a, q, log);
-		if (rc < 0)
-			return finish(rc);
-		log.s += "Trimming complete.\n";
-		return finish(0);
-	}
-	if (!a.empty() && a[0] == '@') { // :146-149
-		*mode = PGX_TRIM_FASTQ;
-		rc = trim_fastq_device(a, paired, gap, fasta_text, fasta_len);
-	} else {
-		// :152-156: the first line without its first byte
-		std::string first;
-		if (a.size() > 1) {
-			const size_t nl = a.find('\n', 1);
-			first = a.substr(1, (nl == std::string::npos ? a.size() : nl) - 1);
-		}
-		const std::string f7 = host_field(first, 7), f10 = host_field(first, 10);
-		if ((f7 == "1" || f7 == "2") && (f10 == "0" || f10 == "1")) {
-			log.s += "QSEQ file format found.\n";
-			*mode = PGX_TRIM_QSEQ;
-			rc = trim_qseq_device(a, b, gap, t1, t2, fasta_text, fasta_len);
+		if (!a.empty() && a[0] == '@') { // :146-149
+			*mode = PGX_TRIM_FASTQ;
+			PGX_TRY(trim_fastq_device(a, paired, gap, fasta_text, fasta_len));
 		} else {
-			log.s += "Error: file format not recognized.\n";
-			*mode = PGX_TRIM_UNKNOWN;
-			*fasta_text = (char *)calloc(1, 1); // RUNBLAST was opened and stays empty (:115)
+			// :152-156: the first line without its first byte
+			std::string first;
+			if (a.size() > 1) {
+				const size_t nl = a.find('\n', 1);
+				first = a.substr(1, (nl == std::string::npos ? a.size() : nl) - 1);
+			}
+			const std::string f7 = host_field(first, 7), f10 = host_field(first, 10);
+			if ((f7 == "1" || f7 == "2") && (f10 == "0" || f10 == "1")) {
+				log.s += "QSEQ file format found.\n";
+				*mode = PGX_TRIM_QSEQ;
+				PGX_TRY(trim_qseq_device(a, b, gap, t1, t2, fasta_text, fasta_len));
+			} else {
+				log.s += "Error: file format not recognized.\n";
+				*mode = PGX_TRIM_UNKNOWN;
+				*fasta_text = (char *)calloc(1, 1); // RUNBLAST was opened and stays empty (:115)
+			}
 		}
-	}
-	if (rc < 0)
-		return finish(rc);
-	log.s += "Trimming complete.\n"; // :167
-	return finish(0);
+		log.s += "Trimming complete.\n"; // :167
+		return 0;
+	});
 }
