@@ -234,6 +234,21 @@ void pgx_reads_close(pgx_reads *r);
 int64_t pgx_reads_count(const pgx_reads *r);
 /* packed bases of read i (2 bits per base, 32 per word, low bits first) for parity checks */
 int pgx_reads_get(const pgx_reads *r, int64_t i, uint8_t *bases_out, int32_t cap, int32_t *len_out);
+/* what the DUST pass (spec S3d) left for a resident batch, whole arrays in one call, for parity checks; reads and changes
+ * nothing.  any_out[n]: read i has a masked base; woff_out[n + 1]: the reads' offsets in 64-bit words, woff_out[n] = the
+ * length of the three word arrays, which must hold `cap_words` >= that many (n_words_out receives it; call with
+ * cap_words = 0 and null arrays to ask).  Read i of length L owns words woff[i] .. woff[i] + (L + 63) / 64 - 1 of each, bit
+ * k of word w = position 64 w + k: mask = the base is masked; win_f / win_r = the 28 bases from that position of the
+ * forward / reverse-complement strand touch no masked base.  The words of a read with any == 0 are UNDEFINED: the
+ * kernels never write them (the seed stage never looks), and the parity tests compare none of them.
+ * pgx_reads_get_dust: the batch's own pass (import, pgx_reads_redo_dust).  pgx_db_get_dust: the handle's own copy, where the
+ * bits of the last search through `db` with pgx_db_set_dust_each_search on landed; `r` is the batch that search was given (a
+ * batch searched piece by piece -- reads with runs of six or more N -- is refused: those bits describe the pieces).  Waits
+ * for the stream that wrote them. */
+int pgx_reads_get_dust(const pgx_reads *r, uint8_t *any_out, uint32_t *woff_out, uint64_t *mask_out, uint64_t *win_f_out,
+		       uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out);
+int pgx_db_get_dust(pgx_db *db, const pgx_reads *r, uint8_t *any_out, uint32_t *woff_out, uint64_t *mask_out, uint64_t *win_f_out,
+		    uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out);
 
 typedef struct {
 	int32_t read, subject;

@@ -94,7 +94,7 @@ SYMBOLS = [
     "pgx_tax_node", "pgx_tax_names", "pgx_tax_format_node", "pgx_tax_format_name", "pgx_tax_cli", "pgx_free",
     "pgx_tax_lineage_batch", "pgx_taxcollect_file", "pgx_consensus_file", "pgx_synth_default", "pgx_db_from_synth",
     "pgx_synth_write_taxdump", "pgx_reads_from_fasta", "pgx_reads_from_fasta_text", "pgx_reads_from_synth", "pgx_reads_write_fasta", "pgx_reads_redo_dust", "pgx_rdp_write_file", "pgx_reads_close", "pgx_reads_count",
-    "pgx_reads_get", "pgx_blast_search", "pgx_hits_close", "pgx_hits_count", "pgx_hits_copy",
+    "pgx_reads_get", "pgx_reads_get_dust", "pgx_db_get_dust", "pgx_blast_search", "pgx_hits_close", "pgx_hits_count", "pgx_hits_copy",
     "pgx_hits_read_offsets", "pgx_hits_read_counts", "pgx_hits_slice", "pgx_hits_format", "pgx_db_bind_taxonomy", "pgx_db_subject_lineage",
     "pgx_rdp_from_file", "pgx_rdp_from_synth", "pgx_rdp_close", "pgx_consensus_batch", "pgx_classify_consensus", "pgx_classify_consensus_tri", "pgx_vote3_batch", "pgx_vote3_format",
     "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_trim_file", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
@@ -124,6 +124,8 @@ def _declare(L):
     sig("pgx_reads_from_fasta", C.c_int, [S, I64, I64, V])
     sig("pgx_reads_from_fasta_text", C.c_int, [C.c_char_p, C.c_size_t, I64, I64, V])
     sig("pgx_reads_get", C.c_int, [V, I64, V, I32, V])
+    sig("pgx_reads_get_dust", C.c_int, [V, V, V, V, V, V, I64, V])
+    sig("pgx_db_get_dust", C.c_int, [V, V, V, V, V, V, V, I64, V])
     sig("pgx_reads_write_fasta", C.c_int, [V, S])
     sig("pgx_reads_redo_dust", C.c_int, [V])
     sig("pgx_rdp_write_file", C.c_int, [V, V, V, S])
@@ -289,12 +291,28 @@ class Db(_Handle):
         """S3d (query masking) recomputed inside every search through this handle, as BLAST runs it"""
         _check(lib().pgx_db_set_dust_each_search(self.ptr, 1 if flag else 0))
 
+    def dust_bits(self, reads):
+        """The handle's own DUST results for `reads` (the last search through it with set_dust_each_search(True)), as
+        Reads.dust_bits() gives the batch's; for parity checks."""
+        return _dust_bits(lambda *a: lib().pgx_db_get_dust(self.ptr, reads.ptr, *a), len(reads))
+
     def bind_taxonomy(self, tax):
         _check(lib().pgx_db_bind_taxonomy(self.ptr, tax.ptr))
 
     def subject_lineage(self, i):
         s = lib().pgx_db_subject_lineage(self.ptr, i)
         return None if s is None else s.decode("latin-1")
+
+
+def _dust_bits(call, n):
+    n_words = C.c_int64()
+    _check(call(None, None, None, None, None, 0, C.byref(n_words)))
+    nw = n_words.value
+    any_ = np.zeros(n, dtype=np.uint8)
+    woff = np.zeros(n + 1, dtype=np.uint32)
+    mask, win_f, win_r = (np.zeros(max(nw, 1), dtype=np.uint64) for _ in range(3))
+    _check(call(any_.ctypes.data, woff.ctypes.data, mask.ctypes.data, win_f.ctypes.data, win_r.ctypes.data, nw, None))
+    return any_, woff, mask[:nw], win_f[:nw], win_r[:nw]
 
 
 class Reads(_Handle):
@@ -325,6 +343,12 @@ class Reads(_Handle):
     def redo_dust(self):
         """Recompute the batch's DUST window bits (what BLAST does inside every search)."""
         _check(lib().pgx_reads_redo_dust(self.ptr))
+
+    def dust_bits(self):
+        """What the batch's DUST pass left, for parity checks: (any[n] uint8, woff[n + 1] uint32, mask, win_f, win_r), the last
+        three uint64 arrays of woff[n] words, one bit per read position from word woff[i] on.  The words of reads with
+        any == 0 are undefined."""
+        return _dust_bits(lambda *a: lib().pgx_reads_get_dust(self.ptr, *a), len(self))
 
     def __len__(self):
         return lib().pgx_reads_count(self.ptr)

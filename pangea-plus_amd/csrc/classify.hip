@@ -2370,6 +2370,21 @@ int pgx_classify_consensus_tri(pgx_db *db, pgx_reads *reads, const pgx_rdp *rdp,
 	return pgx_classify_consensus(db, reads, rdp, hits_out, out, cap);
 }
 
+// the workspace's copy of the DUST results (the last search through `db` with dust_each_search on), for parity checks
+int pgx_db_get_dust(pgx_db *db, const pgx_reads *r, uint8_t *any_out, uint32_t *woff_out, uint64_t *mask_out, uint64_t *win_f_out,
+		    uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out)
+{
+	if (!db || !r)
+		return fail(PGX_E_ARG, "pgx_db_get_dust: null argument");
+	if (r->pieces && r->pieces->n > 0)
+		return fail(PGX_E_ARG, "pgx_db_get_dust: the batch is searched piece by piece, the handle's bits describe the pieces");
+	std::lock_guard<std::mutex> lock(db->search_mu);
+	if (!db->work)
+		return fail(PGX_E_ARG, "pgx_db_get_dust: no search has run through this handle");
+	const Workspace &ws = *static_cast<const Workspace *>(db->work.get());
+	return dust_read_back("pgx_db_get_dust", r, ws.dust, ws.stream, any_out, woff_out, mask_out, win_f_out, win_r_out, cap_words, n_words_out);
+}
+
 int pgx_db_set_dust_each_search(pgx_db *db, int on)
 {
 	if (!db)

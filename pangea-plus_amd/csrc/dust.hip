@@ -454,7 +454,44 @@ int reads_dust_again(const pgx_reads *rd, DustBufs &b, hipStream_t stream)
 	return dust_pass(rd, b, stream);
 }
 
+// What a pass over `rd` left in `b`, for parity checks (pangea_hip.h: pgx_reads_get_dust): plain copies after `stream`.
+int dust_read_back(const char *who, const pgx_reads *rd, const DustBufs &b, hipStream_t stream, uint8_t *any_out, uint32_t *woff_out,
+		   uint64_t *mask_out, uint64_t *win_f_out, uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out)
+{
+	const size_t n = (size_t)rd->n, nw = (size_t)rd->n_words;
+	if (n_words_out)
+		*n_words_out = (int64_t)nw;
+	if (woff_out)
+		std::copy(rd->h_woff.begin(), rd->h_woff.begin() + (ptrdiff_t)std::min(n + 1, rd->h_woff.size()), woff_out);
+	if (!any_out && !mask_out && !win_f_out && !win_r_out)
+		return 0;
+	if ((mask_out || win_f_out || win_r_out) && cap_words < (int64_t)nw)
+		return fail(PGX_E_ARG, "%s: the word arrays hold %lld words, the batch has %lld", who, (long long)cap_words, (long long)nw);
+	if (n == 0)
+		return 0;
+	if (b.any.n < n || b.mask.n < nw || b.win_f.n < nw || b.win_r.n < nw)
+		return fail(PGX_E_ARG, "%s: no DUST pass over a batch of this size has run into these buffers", who);
+	PGX_HIP(hipStreamSynchronize(stream));
+	if (any_out)
+		PGX_TRY(b.any.download(any_out, n));
+	if (mask_out)
+		PGX_TRY(b.mask.download(mask_out, nw));
+	if (win_f_out)
+		PGX_TRY(b.win_f.download(win_f_out, nw));
+	if (win_r_out)
+		PGX_TRY(b.win_r.download(win_r_out, nw));
+	return 0;
+}
+
 } // namespace pgx
+
+extern "C" int pgx_reads_get_dust(const pgx_reads *r, uint8_t *any_out, uint32_t *woff_out, uint64_t *mask_out, uint64_t *win_f_out,
+				  uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out)
+{
+	if (!r)
+		return pgx::fail(PGX_E_ARG, "pgx_reads_get_dust: null argument");
+	return pgx::dust_read_back("pgx_reads_get_dust", r, r->dustb, 0, any_out, woff_out, mask_out, win_f_out, win_r_out, cap_words, n_words_out);
+}
 
 // Recompute the DUST window bits of a resident batch (the same bits: the masks depend on the reads alone).  For callers who
 // count query masking as part of every search -- BLAST runs it per search -- and for bench.py's `dust_in_step` figure.

@@ -209,6 +209,9 @@ int rdp_from_text_device(const char *text, size_t n_bytes, const pgx_reads *read
 // dust.hip
 int reads_dust(pgx_reads *rd);
 int reads_dust_again(const pgx_reads *rd, DustBufs &b, hipStream_t stream);
+// the results of a pass over `rd` in `b`, copied to the host after `stream` (pgx_reads_get_dust, pgx_db_get_dust)
+int dust_read_back(const char *who, const pgx_reads *rd, const DustBufs &b, hipStream_t stream, uint8_t *any_out, uint32_t *woff_out,
+		   uint64_t *mask_out, uint64_t *win_f_out, uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out);
 
 // classify.hip
 struct SearchCounters {

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 from conftest import run_cmd
+from dust_rule import dust_mask   # S3d: the definition of symmetric DUST, stated once (tests/dust_rule.py)
 
 COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
 
@@ -107,35 +108,6 @@ def read_fa(p):
         else:
             out[-1][1] += l.upper()
     return out
-
-
-def dust_mask(seq, W=64, level=20):
-    """S3d: the definition of symmetric DUST (Morgulis et al. 2006): triplet intervals of at most W - 2 triplets whose score
-    (sum of c(c-1)/2 over triplet values, divided by triplets - 1) exceeds level / 10 and is not beaten by a sub-interval."""
-    from fractions import Fraction
-    n, nt = len(seq), len(seq) - 2
-    mask = [False] * n
-    if nt < 2:
-        return mask
-    trip = [seq[i:i + 3] if all(c in "ACGT" for c in seq[i:i + 3]) else None for i in range(nt)]
-    best = {}   # (a, b) -> highest score of any sub-interval of [a, b] with at least two triplets, or None
-    for a in range(nt - 1, -1, -1):
-        cnt, r = {}, 0
-        for b in range(a, min(nt, a + W - 2)):
-            if trip[b] is None:
-                break
-            r += cnt.get(trip[b], 0)
-            cnt[trip[b]] = cnt.get(trip[b], 0) + 1
-            s = Fraction(r, b - a) if b > a else None
-            subs = [x for x in (best.get((a + 1, b)), best.get((a, b - 1))) if x is not None]
-            sub = max(subs) if subs else None
-            if s is not None and s * 10 > level and (sub is None or sub <= s):
-                for k in range(a, b + 3):
-                    mask[k] = True
-            cands = [x for x in (s, sub) if x is not None]
-            best[(a, b)] = max(cands) if cands else None
-    return mask
-
 
 def run_is_seed(qmask, a, b, W=28):
     if b - a < W:
@@ -610,12 +582,21 @@ def test_synthetic_workload_shape(oracle_bin, tmp_path):
         assert len(f) % 3 == 0 and set(f[1::3]) <= {"domain", "phylum", "class", "order", "family", "genus"}
 
 
-def test_dust_trigger_is_necessary_for_a_masked_base():
-    """The device runs the DUST definition only on reads in which the published algorithm's own trigger (10 r_w > 20 L) fires
-    somewhere (csrc/dust.hip).  oracle/fuzz_dust.c: no read with a masked base (definition, o_dust.c) lacks a trigger."""
+def test_dust_trigger_is_necessary_for_a_masked_base(tmp_path):
+    """The device runs the DUST definition only on reads in which the published algorithm's own test (10 r_w > 20 L) passes
+    somewhere, and there only on the triplet intervals [a, b] with a >= first - 61 and b <= last, first and last being the
+    first and the last position that passes (csrc/dust.hip).  oracle/fuzz_dust.c states that first pass by brute force and
+    fails when a read with a masked base (definition, o_dust.c) is not listed, or when the definition restricted to those
+    intervals gives another mask than the whole definition: 60 000 generated reads (every tenth up to 1 500 bases) and
+    the crafted reads of tests/dust_rule.py."""
     import subprocess
     from conftest import ORACLE_DIR
+    from dust_rule import crafted_reads
     subprocess.check_call(["make", "-C", ORACLE_DIR, "bin/fuzz_dust"], stdout=subprocess.DEVNULL)
-    p = subprocess.run([os.path.join(ORACLE_DIR, "bin", "fuzz_dust"), "60000"], capture_output=True, text=True, timeout=300)
+    crafted = crafted_reads()
+    (tmp_path / "crafted.txt").write_text("".join(s + "\n" for _name, s in crafted))
+    p = subprocess.run([os.path.join(ORACLE_DIR, "bin", "fuzz_dust"), "60000", str(tmp_path / "crafted.txt")], capture_output=True, text=True,
+                       timeout=300)
     assert p.returncode == 0, p.stdout + p.stderr
-    assert "counterexamples 0" in p.stdout
+    assert "counterexamples 0" in p.stdout and "range mismatches 0" in p.stdout
+    assert "(from the file %d," % len(crafted) in p.stdout
