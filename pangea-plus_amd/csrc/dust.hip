@@ -14,12 +14,38 @@
 //                 ending at the position.  93 % of random 150-base reads never pass it.  The read sits in NW 64-bit
 //                 registers; the state is ONE LDS word per triplet value (window count + its last four positions), so the
 //                 suffix start moves with the entering triplet alone -- no walk.  Lists the reads with a position that
-//                 passes, with the first and last such position.
+//                 passes, with the first and last such position, the largest r_w up to the last (P) and the first position
+//                 at which a triplet value stood five times in the window (e0).
 // k_dust_perfect  ONE WAVEFRONT per listed read: the definition itself on the stretch the first pass marked, a dynamic
 //                 programme over the interval LENGTH with lane = interval start, neighbours by DPP wave shifts; writes the
 //                 masked bases and whether there are any (an interval above the level exists exactly when a perfect one
 //                 does; the checker's fuzz of the first pass's test against the definition: oracle/fuzz_dust.c).
+//                 Which intervals it looks at, and why no others can matter: "The cuts" below.
 // k_dust_windows  one lane per (listed read with a masked base, 64 positions): the window bits of both strands from the mask
+//
+// The cuts.  The second pass runs the definition on the intervals [a, b] of a listed read with
+//   (0) a >= first - 61, b <= last         the published algorithm finds perfect intervals only at positions that pass its
+//                                          test, and none is longer than 62 (pinned by oracle/fuzz_dust.c)
+//   (1) l <= cap = min(62, (P - 1) / 2 + 1)   an interval of at most 62 triplets that crosses no letter other than a base
+//                                          lies inside the first pass's window at b, so pairs(a, b) <= r_w(b) <= P, the
+//                                          largest r_w of the positions 0 .. last; its score pairs / (l - 1) is above 2
+//                                          only if 2 (l - 1) < P
+//   (3) a >= e0 - cap + 1                  with no value more than 4 times among l triplets, pairs <= 1.5 l, which exceeds
+//                                          2 (l - 1) only for l < 4, and 2 or 3 triplets score at most 1 / 1 and 3 / 2: an
+//                                          interval above the level holds some value five times, so the window count of
+//                                          that value is 5 at its fifth copy, which is at or after e0, the first position at
+//                                          which any count reached 5 -- the interval ends at or after e0 and is at most cap long
+// Every cut drops only intervals that score AT MOST the level.  That is exact: such an interval is no candidate, and as a
+// sub-interval it can never outscore a candidate, so "no score" (Bn / Bq = 0 / 1, what a dead lane carries) stands for it.
+// The intervals that remain are closed under "lies between" (each cut bounds the length, the start or the end), so the
+// best score of a remaining sub-interval still travels to a remaining interval through the two neighbours the recurrence
+// reads.  On uniform random 150-base reads (bench.py) the steps per listed read fall from 62.7 to 22.6, and 1 % of the
+// listed reads need a second chunk of starts where 57 % did (tests/test_dust_cut.py counts both on the CPU).
+//   (2) NOT made: a <= start(last) - 1, the suffix start at `last`.  It holds for every interval above the level (its
+//       first of five copies lies before the suffix start at the fifth), but the recurrence takes pairs(a + 1, b) from the
+//       lane above: lane a is right up to length cap only when the lanes up to a + cap - 2 run as well, and
+//       start(last) + cap - 3 >= last - 1 always (the test passed at `last`: P >= r_w > 2 L, so cap >= L + 1).  A lane that
+//       is missing there spoils the pair counts of the lanes below it (tests/test_dust_cut.py shows the lost mask).
 #include <type_traits>
 
 #include "bitops.hpp"
@@ -37,7 +63,10 @@ __device__ __forceinline__ void dust_wave_sync()
 }
 // One 32-bit word per triplet value and lane: bits 24-29 the value's count in the window of the last 62 triplets, bits
 // 0-23 the positions (mod 64) of its last four occurrences, newest in the low six bits.  65 words per lane: an odd stride
-// (an even one puts the 64 lanes' words on two LDS banks).
+// (an even one puts the 64 lanes' words on two LDS banks).  The bank of lane l's word t is (l + t) mod 32, so the lanes
+// do meet in banks (SQ_LDS_BANK_CONFLICT: 369 M cycles per 10 M reads); the value-major order 64 t + l, bank l mod 32,
+// brought that counter to zero and the kernel from 3.33 to 3.29 ms -- nothing: it waits for the chain read -> count ->
+// write of a position at 2.25 wavefronts per SIMD, not for the LDS array.  Left as it was.
 struct ScanLane {
 	uint32_t w[64];
 	uint32_t pad;
@@ -60,7 +89,7 @@ template <int NR> __device__ __forceinline__ uint64_t reg_window64(const uint64_
 
 // First pass, every read of the batch, one lane per read: the published algorithm's window bookkeeping and its test
 // "10 r_w > 20 L" (header), without which it never looks for a perfect interval ending at a position.  Lists the reads with
-// a position that passes, with the first and last such position.
+// a position that passes, with the first and last such position, P and e0 (header: the cuts).
 //   r_w  pairs of equal triplets in the window of the last (at most) 62 triplets: the entering triplet adds its count, the
 //        leaving one takes its count - 1 away.
 //   L    length of the window's longest suffix in which no triplet occurs more than 4 times.  Only the ENTERING triplet can
@@ -74,7 +103,7 @@ template <int NR> __device__ __forceinline__ uint64_t reg_window64(const uint64_
 template <int NW>
 __global__ __launch_bounds__(64) void k_dust_scan(const uint64_t *__restrict__ fwd, const uint64_t *__restrict__ amb,
 						   const uint32_t *__restrict__ len, const uint32_t *__restrict__ woff, uint32_t n,
-						   uint32_t *__restrict__ list, uint2 *__restrict__ range, uint32_t *__restrict__ n_list)
+						   uint32_t *__restrict__ list, uint4 *__restrict__ range, uint32_t *__restrict__ n_list)
 {
 	constexpr bool REGS = NW > 0;
 	constexpr int NR = REGS ? NW + 1 : 1;
@@ -94,6 +123,9 @@ __global__ __launch_bounds__(64) void k_dust_scan(const uint64_t *__restrict__ f
 	for (int k = 0; k < 64; k++)
 		tab[k] = 0u;
 	int first = -1, last = -1;
+	// for the second pass's cuts: the largest r_w of any position so far and its value at `last`; the first position at
+	// which a triplet value stood five times in the window
+	int p_max = 0, p_last = 0, e0 = -1;
 	int size = 0, start = 0, rw_pairs = 0; // the window is the `size` triplets that end at the current one; the suffix starts at `start`
 	// the entering and the leaving triplet come from two 64-bit registers that hold 32 letters each (refilled every 16 positions)
 	uint64_t in_w = 0, out_w = 0;
@@ -165,13 +197,16 @@ __global__ __launch_bounds__(64) void k_dust_scan(const uint64_t *__restrict__ f
 				const int d = (b - (int)((wt >> 18) & 63u)) & 63; // 4 .. 61 positions back
 				const int cand = b - d + 1;
 				start = cand > start ? cand : start;
+				e0 = e0 < 0 ? b : e0;
 			}
 			tab[t] = (((wt << 6) | (uint32_t)(b & 63)) & 0xFFFFFFu) | ((uint32_t)cnt << 24);
 			int L = b - start + 1;
 			L = L < size ? L : size;
+			p_max = rw_pairs > p_max ? rw_pairs : p_max;
 			if (rw_pairs * 10 > L * kDustLevel) {
 				first = first < 0 ? b : first;
 				last = b;
+				p_last = p_max;
 			}
 		}
 	}
@@ -186,14 +221,15 @@ __global__ __launch_bounds__(64) void k_dust_scan(const uint64_t *__restrict__ f
 		if (first >= 0) {
 			const uint32_t at = base + (uint32_t)__popcll(listed & ((1ull << (threadIdx.x & 63)) - 1ull));
 			list[at] = r;
-			range[at] = make_uint2((uint32_t)first, (uint32_t)last);
+			range[at] = make_uint4((uint32_t)first, (uint32_t)last, (uint32_t)p_last, (uint32_t)e0);
 		}
 	}
 }
 
 // Second pass, ONE WAVEFRONT per listed read: the definition itself (header) on the stretch where the first pass's test
-// passed -- intervals [a, b] of at most 62 triplets with a >= first - 61 and b <= last -- as a dynamic programme over the
-// interval LENGTH: lane j holds the start a = a0 + j, step l every lane's interval [a, a + l - 1].
+// passed -- intervals [a, b] of at most cap triplets with a >= max(first - 61, e0 - cap + 1) and b <= last (header: the
+// cuts) -- as a dynamic programme over the interval LENGTH: lane j holds the start a = a0 + j, step l every lane's
+// interval [a, a + l - 1].
 //   pairs(a, b) = pairs(a + 1, b) + pairs(a, b - 1) - pairs(a + 1, b - 1) + [t_a = t_b]
 //   best(a, b)  = max(score(a, b), best(a + 1, b), best(a, b - 1))      (exact fractions, a missing score below all)
 // so a step needs lane j + 1's values of the two steps before (two DPP wave shifts) and the triplet at the interval's end
@@ -210,24 +246,40 @@ __device__ __forceinline__ int dust_dpp_up(int v, int last_lane_value) // lane j
 
 __global__ __launch_bounds__(64) void k_dust_perfect(const uint64_t *__restrict__ fwd, const uint64_t *__restrict__ amb,
 						      const uint32_t *__restrict__ len, const uint32_t *__restrict__ woff,
-						      const uint32_t *__restrict__ list, const uint2 *__restrict__ range, const uint32_t *__restrict__ n_list,
+						      const uint32_t *__restrict__ list, const uint4 *__restrict__ range, const uint32_t *__restrict__ n_list,
 						      uint64_t *__restrict__ mask, uint8_t *__restrict__ any)
 {
 	// lane 0's sequences (pairs, best score as numerator and denominator; index = interval length) of the chunk above
 	__shared__ uint32_t s_up[3][64];
 	const int lane = (int)(threadIdx.x & 63);
 	const uint32_t n_in = *n_list;
-	for (uint32_t at = blockIdx.x; at < n_in; at += gridDim.x) {
-		const uint32_t r = list[at];
-		const int L = (int)len[r], nt = L - 2;
-		const uint64_t *rw = fwd + woff[r], *ra = amb ? amb + woff[r] : nullptr;
-		uint64_t *mw = mask + woff[r];
+	if (blockIdx.x >= n_in)
+		return;
+	// The head of a read is a chain of dependent loads (list -> len, woff -> letters) that the steps used to hide; with a
+	// third of the steps it shows.  So a read's words are asked for one read ahead, its number two reads ahead, and they
+	// arrive while the letters of the current read do.  (Past the list's end the current entry is asked for again.)
+	uint32_t at = blockIdx.x;
+	uint32_t r = list[at];
+	uint4 rg = range[at]; // first, last, P, e0
+	uint32_t L_r = len[r], w_r = woff[r];
+	uint32_t r_next = list[at + gridDim.x < n_in ? at + gridDim.x : at];
+	for (;;) {
+		const uint32_t at_next = at + gridDim.x, at_after = at_next + gridDim.x;
+		const bool more = at_next < n_in;
+		const uint4 rg_next = range[more ? at_next : at];
+		const uint32_t L_next = len[r_next], w_next = woff[r_next];
+		const uint32_t r_after = list[at_after < n_in ? at_after : at];
+		const int L = (int)L_r, nt = L - 2;
+		const uint64_t *rw = fwd + w_r, *ra = amb ? amb + w_r : nullptr;
+		uint64_t *mw = mask + w_r;
 		const int nw = (L + 63) >> 6;
 		for (int w = lane; w < nw; w += 64)
-			mw[w] = 0ull;
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the words are zero before any lane ORs into them)
-		const int b_hi = (int)range[at].y < nt - 1 ? (int)range[at].y : nt - 1;
-		const int a_lo = (int)range[at].x - (kDustMaxT - 1) > 0 ? (int)range[at].x - (kDustMaxT - 1) : 0;
+			mw[w] = 0ull; // (in memory before any lane ORs into them: the wait in front of the marking below)
+		const int b_hi = (int)rg.y < nt - 1 ? (int)rg.y : nt - 1;
+		const int cap = ((int)rg.z - 1) / 2 + 1 < kDustMaxT ? ((int)rg.z - 1) / 2 + 1 : kDustMaxT; // (a listed read has P >= 3)
+		const int a_old = (int)rg.x - (kDustMaxT - 1), a_new = (int)rg.w - cap + 1;
+		const int a_cut = a_old > a_new ? a_old : a_new;
+		const int a_lo = a_cut > 0 ? a_cut : 0;
 		const int n_chunks = (b_hi - a_lo + 64) / 64;
 		bool marked = false;
 		for (int c = n_chunks - 1; c >= 0; c--) {
@@ -250,7 +302,7 @@ __global__ __launch_bounds__(64) void k_dust_perfect(const uint64_t *__restrict_
 			uint32_t P1 = 0, P2 = 0, Bn = 0, Bq = 1;
 			uint32_t myP = 0, myN = 0, myQ = 1; // lane l: lane 0's values at length l
 			int end = -1;                       // furthest base a perfect interval of this start covers
-			const int l_max = b_hi - a0 + 1 < kDustMaxT ? b_hi - a0 + 1 : kDustMaxT; // (lane 0's reach; the other lanes die earlier)
+			const int l_max = b_hi - a0 + 1 < cap ? b_hi - a0 + 1 : cap; // (lane 0's reach; the other lanes die earlier)
 			// (two copies of the loop: without a chunk above -- the only chunk of most reads -- lane 63's neighbour values are
 			// constants, which lets the compiler fold the wave shifts into the instructions that use them)
 			auto steps = [&](auto UP) {
@@ -303,6 +355,7 @@ __global__ __launch_bounds__(64) void k_dust_perfect(const uint64_t *__restrict_
 				s_up[2][lane] = myQ;
 				dust_wave_sync();
 			}
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the read's mask words are zero by now)
 			if (end >= 0) {
 				marked = true;
 				for (int k = a; k <= end;) {
@@ -316,7 +369,14 @@ __global__ __launch_bounds__(64) void k_dust_perfect(const uint64_t *__restrict_
 		}
 		if (__ballot(marked) && lane == 0)
 			any[r] = 1;
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		if (!more)
+			break;
+		at = at_next;
+		r = r_next;
+		rg = rg_next;
+		L_r = L_next;
+		w_r = w_next;
+		r_next = r_after;
 	}
 }
 

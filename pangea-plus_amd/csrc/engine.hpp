@@ -91,7 +91,8 @@ struct DustBufs {
 	DevBuf<uint8_t> any;            // per read: it has a masked base
 	DevBuf<uint64_t> mask;          // the masked bases of the listed reads
 	DevBuf<uint32_t> list, n;       // reads the first pass listed, their number (on the device)
-	DevBuf<uint2> range;            // first and last position of a listed read at which the algorithm's test passes
+	DevBuf<uint4> range;            // per listed read: first and last position at which the algorithm's test passes, the largest
+				       // window pair count up to the last, the first position with five copies of a value in the window
 };
 } // namespace pgx
 
