@@ -11,11 +11,13 @@
 // k_dust_scan<NW>   every read, one lane per read, linear: the published algorithm's own bookkeeping (the window of the last 62
 //                 triplets with its pair count r_w; L, the length of its longest suffix in which no triplet occurs more than
 //                 4 times) and its test "10 r_w > 20 L", without which that algorithm never looks for a perfect interval
-//                 ending at the position.  93 % of random 150-base reads never pass it.  The read sits in NW 64-bit
-//                 registers; the state is ONE LDS word per triplet value (window count + its last four positions), so the
-//                 suffix start moves with the entering triplet alone -- no walk.  Lists the reads with a position that
-//                 passes, with the first and last such position, the largest r_w up to the last (P) and the first position
-//                 at which a triplet value stood five times in the window (e0).
+//                 ending at the position.  93 % of random 150-base reads never pass it.  The state is ONE LDS word per
+//                 triplet value (window count + its last four positions), so the suffix start moves with the entering
+//                 triplet alone -- no walk.  NW > 0: the read sits in registers, a word changes by LDS atomics only, and a
+//                 position's atomics are issued before the arithmetic of the position before it: no LDS round trip on the
+//                 chain from position to position.  NW = 0: any length, ambiguity letters, letters from memory.  Lists the
+//                 reads with a position that passes, with the first and last such position, the largest r_w up to the
+//                 last (P) and the first position at which a triplet value stood five times in the window (e0).
 // k_dust_perfect  ONE WAVEFRONT per listed read: the definition itself on the stretch the first pass marked, a dynamic
 //                 programme over the interval LENGTH with lane = interval start, neighbours by DPP wave shifts; writes the
 //                 masked bases and whether there are any (an interval above the level exists exactly when a perfect one
@@ -61,31 +63,26 @@ __device__ __forceinline__ void dust_wave_sync()
 	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 	__builtin_amdgcn_wave_barrier();
 }
-// One 32-bit word per triplet value and lane: bits 24-29 the value's count in the window of the last 62 triplets, bits
-// 0-23 the positions (mod 64) of its last four occurrences, newest in the low six bits.  65 words per lane: an odd stride
-// (an even one puts the 64 lanes' words on two LDS banks).  The bank of lane l's word t is (l + t) mod 32, so the lanes
-// do meet in banks (SQ_LDS_BANK_CONFLICT: 369 M cycles per 10 M reads); the value-major order 64 t + l, bank l mod 32,
-// brought that counter to zero and the kernel from 3.33 to 3.29 ms -- nothing: it waits for the chain read -> count ->
-// write of a position at 2.25 wavefronts per SIMD, not for the LDS array.  Left as it was.
+// One 32-bit word per triplet value and lane (its fields: at the two forms of the scan below), and a spare one.  65 words
+// per lane: an odd stride (an even one puts the 64 lanes' words on two LDS banks).  The bank of lane l's word t is
+// (l + t) mod 32, so the lanes do meet in banks; with round 4's read-and-write loop (SQ_LDS_BANK_CONFLICT: 369 M cycles per
+// 10 M reads) the value-major order 64 t + l, bank l mod 32, brought that counter to zero and the kernel from 3.33 to
+// 3.29 ms -- nothing: it waited for the chain of a position, not for the LDS array.  Left as it was.
 struct ScanLane {
 	uint32_t w[64];
 	uint32_t pad;
 };
 static_assert(sizeof(ScanLane) / 4 % 2 == 1, "odd word stride");
 
-// 64 bits of a read held in registers (R[k] = its k-th word, R[NW] .. = 0), from base `pos`; `pos` is the same in every lane
-template <int NR> __device__ __forceinline__ uint64_t reg_window64(const uint64_t (&R)[NR], int pos)
-{
-	const int wi = __builtin_amdgcn_readfirstlane(pos >> 5), sh = (pos & 31) * 2;
-	uint64_t lo = 0, hi = 0;
-#pragma unroll
-	for (int k = 0; k + 1 < NR; k++)
-		if (wi == k) {
-			lo = R[k];
-			hi = R[k + 1];
-		}
-	return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-}
+// The register form's table word (one per triplet value and lane, ScanLane): bits 24-29 the value's count in the window of
+// the last 62 triplets, bits 30-31 the number of its occurrences so far mod 4, bits 0-23 four slots of six bits with the
+// positions (mod 64) of its last four occurrences, occurrence number n in slot n mod 4.  Every change of a word is ONE LDS
+// atomic whose operand does not depend on what an earlier one returned for the count fields: the leaving triplet subtracts
+// kScanLeave, the entering one adds kScanEnter (the count fields sit above the slots and the window count never leaves
+// 0 .. 62, so neither carries into another field), and the entering position replaces the oldest slot by an XOR with
+// (old slot ^ position).  The two returns give everything a position computes.
+constexpr uint32_t kScanLeave = 1u << 24, kScanEnter = (1u << 24) + (1u << 30);
+static_assert(kDustLevel % 10 == 0, "the test 10 r_w > level * L as r_w > (level / 10) * L");
 
 // First pass, every read of the batch, one lane per read: the published algorithm's window bookkeeping and its test
 // "10 r_w > 20 L" (header), without which it never looks for a perfect interval ending at a position.  Lists the reads with
@@ -95,121 +92,215 @@ template <int NR> __device__ __forceinline__ uint64_t reg_window64(const uint64_
 //   L    length of the window's longest suffix in which no triplet occurs more than 4 times.  Only the ENTERING triplet can
 //        move that suffix's start: to just behind its own fifth-most-recent occurrence, if that lies inside the window --
 //        which the triplet's window count says (5 or more with the entering one) and the triplet's last four positions
-//        give.  Both live in ONE LDS word per triplet value (ScanLane): a position costs two reads and two writes.
+//        give.  Both live in ONE LDS word per triplet value (ScanLane).
 //        Round 3 kept a second set of counters for the suffix and, when a count there reached 5, walked the suffix for its
 //        earliest copy -- the whole wavefront for one lane's walk, some lane at most positions: ~1 500 cycles a position.
-// NW > 0: reads of at most 32 NW bases without ambiguity letters, the whole read in NW 64-bit registers per lane -- no
-// memory access inside the loop; NW = 0: any length, ambiguity flags, letters from memory every 16 positions.
+// NW > 0 (dust_scan_regs): reads of at most 32 NW bases without ambiguity letters, the whole read in registers -- no memory
+// access inside the loop, and no LDS round trip on the chain from one position to the next;  NW = 0 (dust_scan_mem): any
+// length, ambiguity flags, letters from memory every 16 positions, a position waits for its two reads and two writes.
+//
+// The register form.  Round 4's loop read tab[t], computed, read and wrote tab[s0], wrote tab[t]: two LDS round trips on
+// the chain of every position at 2.25 wavefronts per SIMD (LDS holds 9 tables per CU), 49 vector instructions a position,
+// the SIMD idle half the time.  Here
+//   * the leaving triplet's word is decremented FIRST (LDS operations of a wavefront complete in order), so the entering
+//     one's return is its count after the removal and "the same value leaves and enters" is no case of its own;
+//   * the operands of a position's two returning atomics come from the read's registers alone, so they are issued one
+//     position AHEAD, before the arithmetic of the position before them; the slot XOR of position b is issued behind the
+//     atomics of b + 1 -- it touches slot n mod 4 of its value, they read slot n + 1 when the value is the same, and the
+//     next reader of slot n is that value's occurrence n + 4, at least three positions on;
+//   * 16 positions are one block of straight-line code, so every letter is a bit-field extract at a constant offset from
+//     the block's two windows, which stand in fixed registers: the read moves down one register per block; the blocks in
+//     which the window fills (nothing leaves) have code of their own;
+//   * first, last and P are kept behind a branch that 86 % of the positions of random reads skip with every lane; the
+//     lanes past their read's end run on (the table indices are six bits whatever the letters) and are masked there.
+template <int NW>
+__device__ __forceinline__ void dust_scan_regs(uint32_t *tab, const uint64_t *rw, int nt, int &first, int &last, int &p_last, int &e0)
+{
+	// 16 letters per register.  The block of positions 16 j .. 16 j + 15 takes its entering letters from the registers j, j + 1
+	// of the read and its leaving ones from j - 4, j - 3 (position b drops the triplet at b - 62: letter k + 2 there).  They
+	// stand in D[4], D[5] and D[0], D[1] for every block: four registers of zeros in front of the read, two behind (the
+	// packed reads carry spare words behind every read), and the whole array moves down one register after a block.
+	constexpr int ND = 2 * NW + 6;
+	uint32_t D[ND];
+#pragma unroll
+	for (int k = 0; k < NW; k++) {
+		const uint2 w = reinterpret_cast<const uint2 *>(rw)[k];
+		D[4 + 2 * k] = w.x;
+		D[5 + 2 * k] = w.y;
+	}
+	D[0] = D[1] = D[2] = D[3] = D[ND - 2] = D[ND - 1] = 0u;
+	int nt_wave = nt; // every lane runs to the longest read's end
+	for (int sh = 1; sh < 64; sh <<= 1) {
+		const int o = __shfl_xor(nt_wave, sh);
+		nt_wave = o > nt_wave ? o : nt_wave;
+	}
+	nt_wave = __builtin_amdgcn_readfirstlane(nt_wave);
+	// L itself is kept, not the suffix's start: one more than at the position before, cut to the distance back to the entering
+	// triplet's fifth-most-recent occurrence when the window holds five, and to the window's 62 (the count while it fills)
+	int L = -1, rw_pairs = 0, p_max = 0, e0_min = 0x7fffffff;
+	// The position whose atomics are out: what they returned, and its word.  In front of position 0 stands a position -1 that
+	// changes nothing but L, from -1 to 0: no pairs, a leaving count of 1, the lane's spare word.
+	uint32_t old_s = kScanLeave, old_t = 0u, *at_t = tab + 64;
+	auto finish = [&](int b) __attribute__((always_inline)) {
+		const int cnt = (int)__builtin_amdgcn_ubfe(old_t, 24, 6); // the entering triplet's count in the window without itself
+		const int cs = (int)__builtin_amdgcn_ubfe(old_s, 24, 6);  // the leaving triplet's, itself included (1: nothing left)
+		rw_pairs += cnt - cs + 1;
+		// its fifth-most-recent occurrence is the oldest slot, valid when the window holds five; the position takes that slot
+		const uint32_t sh = (old_t >> 30) * 6u;
+		const uint32_t o = (old_t >> sh) & 63u;
+		__hip_atomic_fetch_xor(at_t, (o ^ (uint32_t)(b & 63)) << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		const bool five = cnt >= 4;
+		const int d = (b - (int)o) & 63; // 4 .. 61 positions back: the suffix starts just behind it
+		L = min(L + 1, five ? d : kDustMaxT);
+		e0_min = min(e0_min, five ? b : 0x7fffffff);
+		p_max = max(p_max, rw_pairs);
+		if (rw_pairs > L * (kDustLevel / 10)) {
+			// (rare: 86 % of the positions of random reads pass in no lane.  The empty statement keeps the branch over
+			// these lines: without it they are predicated and issued at every position)
+			asm volatile("");
+			const bool mine = b < nt;
+			first = mine && first < 0 ? b : first;
+			last = mine ? b : last;
+			p_last = mine ? p_max : p_last;
+		}
+	};
+	// position b = 16 j + k: its two atomics, then the arithmetic of position b - 1 behind them (the scheduler would
+	// otherwise put the uses of what b - 1's atomics returned in front of b's, and wait there)
+	auto step = [&](int b, int k, bool full) __attribute__((always_inline)) {
+		// (the letters as opaque registers: the address is then one shift-and-add; left to itself the compiler merges the
+		// extract with the address's shift into three instructions)
+		uint32_t ns = kScanLeave;
+		if (full) {
+			uint32_t s0 = k + 2 < 14 ? __builtin_amdgcn_ubfe(D[0], 2 * (k + 2), 6) : (uint32_t)((((uint64_t)D[0] | ((uint64_t)D[1] << 32)) >> (2 * k + 4)) & 63ull);
+			asm("" : "+v"(s0));
+			ns = __hip_atomic_fetch_sub(tab + s0, kScanLeave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		}
+		uint32_t t = k < 14 ? __builtin_amdgcn_ubfe(D[4], 2 * k, 6) : (uint32_t)((((uint64_t)D[4] | ((uint64_t)D[5] << 32)) >> (2 * k)) & 63ull);
+		asm("" : "+v"(t));
+		uint32_t *at = tab + t;
+		const uint32_t nv = __hip_atomic_fetch_add(at, kScanEnter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		__builtin_amdgcn_sched_barrier(0);
+		finish(b - 1);
+		old_s = ns;
+		old_t = nv;
+		at_t = at;
+	};
+	auto move_down = [&]() __attribute__((always_inline)) {
+#pragma unroll
+		for (int i = 0; i + 1 < ND; i++)
+			D[i] = D[i + 1];
+	};
+	int b0 = 0;
+	// whole blocks, straight-line: positions 0 .. 47 fill the window, 62 is the first with a leaving triplet
+	for (; b0 + 16 <= nt_wave; b0 += 16) {
+		if (b0 < 48) {
+#pragma unroll
+			for (int k = 0; k < 16; k++)
+				step(b0 + k, k, false);
+		} else if (b0 == 48) {
+#pragma unroll
+			for (int k = 0; k < 16; k++)
+				step(48 + k, k, 48 + k >= kDustMaxT);
+		} else {
+#pragma unroll
+			for (int k = 0; k < 16; k++)
+				step(b0 + k, k, true);
+		}
+		move_down();
+	}
+	// the rest of the longest read, fewer than 16 positions
+	for (int b = b0; b < nt_wave; b++)
+		step(b, b - b0, b >= kDustMaxT);
+	finish(nt_wave - 1);
+	e0 = e0_min;
+}
+
+// The memory form: the same bookkeeping with the table word read and written (bits 24-29 the count, bits 0-23 the last
+// four positions, newest in the low six bits); a letter that is no base empties the window.
+__device__ __forceinline__ void dust_scan_mem(uint32_t *tab, const uint64_t *rw, const uint64_t *ra, int nt, int &first, int &last, int &p_last, int &e0)
+{
+	int p_max = 0;
+	int size = 0, start = 0, rw_pairs = 0; // the window is the `size` triplets that end at the current one; the suffix starts at `start`
+	// the entering and the leaving triplet come from two 64-bit registers that hold 32 letters each (refilled every 16 positions)
+	uint64_t in_w = 0, out_w = 0;
+	int out_pos = -1;
+	for (int b = 0; b < nt; b++) {
+		if ((b & 15) == 0)
+			in_w = window64(rw, b);
+		int t = (int)(in_w & 63ull);
+		in_w >>= 2;
+		if (ra && (window64(ra, b) & 0x15ull))
+			t = -1;
+		if (t < 0) { // a letter that is no base: no interval crosses it
+			for (int k = 0; k < 64; k++)
+				tab[k] = 0u;
+			size = rw_pairs = 0;
+			start = b + 1;
+			continue;
+		}
+		uint32_t wt = tab[t];
+		int cnt = (int)(wt >> 24); // the entering triplet's count in the window, itself included (below)
+		if (size >= kDustMaxT) {
+			// the oldest triplet leaves: position b - 62 (the window was full, so it is 62 triplets behind)
+			const int ob = b - kDustMaxT;
+			if (ob != out_pos || (ob & 15) == 0) {
+				out_w = window64(rw, ob);
+				out_pos = ob;
+			}
+			const int s0 = (int)(out_w & 63ull);
+			out_w >>= 2;
+			out_pos++;
+			if (s0 != t) {
+				const uint32_t ws = tab[s0];
+				tab[s0] = ws - (1u << 24);
+				rw_pairs += cnt - ((int)(ws >> 24) - 1);
+				cnt++;
+			} // (the same triplet leaving and entering: its count and the pair sum end where they were)
+		} else {
+			size++;
+			rw_pairs += cnt;
+			cnt++;
+		}
+		// its fifth-most-recent occurrence = the oldest of the four positions kept, valid when the window holds five
+		if (cnt >= 5) {
+			const int d = (b - (int)((wt >> 18) & 63u)) & 63; // 4 .. 61 positions back
+			const int cand = b - d + 1;
+			start = cand > start ? cand : start;
+			e0 = e0 < 0 ? b : e0;
+		}
+		tab[t] = (((wt << 6) | (uint32_t)(b & 63)) & 0xFFFFFFu) | ((uint32_t)cnt << 24);
+		int L = b - start + 1;
+		L = L < size ? L : size;
+		p_max = rw_pairs > p_max ? rw_pairs : p_max;
+		if (rw_pairs * 10 > L * kDustLevel) {
+			first = first < 0 ? b : first;
+			last = b;
+			p_last = p_max;
+		}
+	}
+}
+
 template <int NW>
 __global__ __launch_bounds__(64) void k_dust_scan(const uint64_t *__restrict__ fwd, const uint64_t *__restrict__ amb,
 						   const uint32_t *__restrict__ len, const uint32_t *__restrict__ woff, uint32_t n,
 						   uint32_t *__restrict__ list, uint4 *__restrict__ range, uint32_t *__restrict__ n_list)
 {
-	constexpr bool REGS = NW > 0;
-	constexpr int NR = REGS ? NW + 1 : 1;
 	__shared__ ScanLane s_lane[64];
 	uint32_t *tab = s_lane[threadIdx.x].w;
 	const uint32_t at0 = blockIdx.x * 64u + threadIdx.x;
 	const bool has_read = at0 < n;
 	const uint32_t r = has_read ? at0 : 0u;
 	const int nt = has_read ? (int)len[r] - 2 : 0;
-	const uint64_t *rw = fwd + woff[r], *ra = (!REGS && amb) ? amb + woff[r] : nullptr;
-	uint64_t R[NR];
-	if constexpr (REGS) {
-#pragma unroll
-		for (int k = 0; k < NR; k++)
-			R[k] = k < NW ? rw[k] : 0ull; // (the packed reads carry spare words behind every read)
-	}
+	const uint64_t *rw = fwd + woff[r];
 	for (int k = 0; k < 64; k++)
 		tab[k] = 0u;
-	int first = -1, last = -1;
-	// for the second pass's cuts: the largest r_w of any position so far and its value at `last`; the first position at
-	// which a triplet value stood five times in the window
-	int p_max = 0, p_last = 0, e0 = -1;
-	int size = 0, start = 0, rw_pairs = 0; // the window is the `size` triplets that end at the current one; the suffix starts at `start`
-	// the entering and the leaving triplet come from two 64-bit registers that hold 32 letters each (refilled every 16 positions)
-	uint64_t in_w = 0, out_w = 0;
-	int out_pos = -1;
-	int nt_wave = nt; // (REGS: the refills are the wavefront's, every lane runs to the longest read's end)
-	if constexpr (REGS) {
-		for (int sh = 1; sh < 64; sh <<= 1) {
-			const int o = __shfl_xor(nt_wave, sh);
-			nt_wave = o > nt_wave ? o : nt_wave;
-		}
-	}
-	for (int b = 0; b < nt_wave; b++) {
-		int t = -1;
-		if constexpr (REGS) {
-			if ((b & 15) == 0)
-				in_w = reg_window64(R, b);
-			if (b >= kDustMaxT && ((b - kDustMaxT) & 15) == 0)
-				out_w = reg_window64(R, b - kDustMaxT); // (every lane whose window is full is at the same position b - 62)
-		}
-		if (b < nt) {
-			if constexpr (REGS) {
-				t = (int)((in_w >> (2 * (b & 15))) & 63ull);
-			} else {
-				if ((b & 15) == 0)
-					in_w = window64(rw, b);
-				t = (int)(in_w & 63ull);
-				in_w >>= 2;
-				if (ra && (window64(ra, b) & 0x15ull))
-					t = -1;
-				if (t < 0) { // a letter that is no base: no interval crosses it
-					for (int k = 0; k < 64; k++)
-						tab[k] = 0u;
-					size = rw_pairs = 0;
-					start = b + 1;
-				}
-			}
-		}
-		if (t >= 0) {
-			uint32_t wt = tab[t];
-			int cnt = (int)(wt >> 24); // the entering triplet's count in the window, itself included (below)
-			if (size >= kDustMaxT) {
-				// the oldest triplet leaves: position b - 62 (the window was full, so it is 62 triplets behind)
-				const int ob = b - kDustMaxT;
-				int s0;
-				if constexpr (REGS) {
-					s0 = (int)((out_w >> (2 * (ob & 15))) & 63ull);
-				} else {
-					if (ob != out_pos || (ob & 15) == 0) {
-						out_w = window64(rw, ob);
-						out_pos = ob;
-					}
-					s0 = (int)(out_w & 63ull);
-					out_w >>= 2;
-					out_pos++;
-				}
-				if (s0 != t) {
-					const uint32_t ws = tab[s0];
-					tab[s0] = ws - (1u << 24);
-					rw_pairs += cnt - ((int)(ws >> 24) - 1);
-					cnt++;
-				} // (the same triplet leaving and entering: its count and the pair sum end where they were)
-			} else {
-				size++;
-				rw_pairs += cnt;
-				cnt++;
-			}
-			// its fifth-most-recent occurrence = the oldest of the four positions kept, valid when the window holds five
-			if (cnt >= 5) {
-				const int d = (b - (int)((wt >> 18) & 63u)) & 63; // 4 .. 61 positions back
-				const int cand = b - d + 1;
-				start = cand > start ? cand : start;
-				e0 = e0 < 0 ? b : e0;
-			}
-			tab[t] = (((wt << 6) | (uint32_t)(b & 63)) & 0xFFFFFFu) | ((uint32_t)cnt << 24);
-			int L = b - start + 1;
-			L = L < size ? L : size;
-			p_max = rw_pairs > p_max ? rw_pairs : p_max;
-			if (rw_pairs * 10 > L * kDustLevel) {
-				first = first < 0 ? b : first;
-				last = b;
-				p_last = p_max;
-			}
-		}
-	}
+	// the first and the last position that pass; for the second pass's cuts: the largest r_w of any position up to `last`,
+	// and the first position at which a triplet value stood five times in the window
+	int first = -1, last = -1, p_last = 0, e0 = -1;
+	if constexpr (NW > 0)
+		dust_scan_regs<NW>(tab, rw, nt, first, last, p_last, e0);
+	else
+		dust_scan_mem(tab, rw, amb ? amb + woff[r] : nullptr, nt, first, last, p_last, e0);
 	// one atomic per wavefront (a single counter takes ~90 M atomics a second: one per listed read was most of this kernel)
 	const unsigned long long listed = __ballot(first >= 0);
 	if (listed) {
