@@ -62,6 +62,21 @@ __device__ __forceinline__ void lds_sync()
 	__builtin_amdgcn_wave_barrier();
 }
 
+// The lane's number, formed where it is used.  In the lane-per-HSP kernels every vector register that lives across the
+// rows is a spill, and a spill there is memory traffic, so what two instructions give back is not
+// kept: `volatile` keeps the compiler from hoisting it out of the round loop and carrying it.
+__device__ __forceinline__ uint32_t lane_here()
+{
+	uint32_t l;
+	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+	return l;
+}
+// set bits of a ballot below this lane (no per-lane mask to build or to keep)
+__device__ __forceinline__ uint32_t ballot_rank(unsigned long long m)
+{
+	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 struct GapSeqs {
 	const uint64_t *rw, *ra;   // read strand: words, spaced ambiguity flags (or null)
 	const uint64_t *dbw, *dba; // database words, flags (or null)
@@ -430,10 +445,12 @@ typedef __attribute__((address_space(3))) uint32_t lds_word;
 typedef __attribute__((address_space(3))) char lds_byte;
 // (the rows' base stays a link-time constant that folds into the instruction's offset field; `off` = row * 256 | lane * 4)
 __device__ __forceinline__ uint32_t lds_ld(const lds_word *seq0, uint32_t off) { return *(const lds_word *)((const lds_byte *)seq0 + off); }
-__device__ __forceinline__ uint32_t min3u(uint32_t a, uint32_t b, uint32_t c)
+
+// min(a, 32, c): the 32 as the instruction's inline constant (as a "v" operand it sat in a register of its own all through the rows)
+__device__ __forceinline__ uint32_t min3u_32(uint32_t a, uint32_t c)
 {
 	uint32_t r;
-	asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+	asm("v_min3_u32 %0, %1, 32, %2" : "=v"(r) : "v"(a), "v"(c));
 	return r;
 }
 
@@ -450,7 +467,7 @@ __device__ __forceinline__ uint32_t lean_lcp(const lds_word *seq0, uint32_t lane
 	const uint32_t qa = ((qb << 3) & 0xFFFFFF00u) | lane4, da = ((db << 3) & 0xFFFFFF00u) | lane4;
 	const uint32_t x = __builtin_amdgcn_alignbit(lds_ld(seq0, qa + 256), lds_ld(seq0, qa), qb) ^ __builtin_amdgcn_alignbit(lds_ld(seq0, da + 256), lds_ld(seq0, da), db);
 	const uint32_t y = (x | (x >> 1)) & 0x55555555u;
-	return min3u(scan_low(y), 32u, cap2);
+	return min3u_32(scan_low(y), cap2);
 }
 
 // status: 0 done, 1 cells alive after D differences (next tier), 2 the best cell holds two or more gap columns of a kind (next tier)
@@ -538,7 +555,7 @@ __device__ __forceinline__ int greedy_rows_lean(const lds_word *seq0, uint32_t l
 		const bool ok = ((m3 | cap2) >= 0) & (rk <= width);
 		const uint32_t x = __builtin_amdgcn_alignbit(lds_ld(seq0, qa + 256), lds_ld(seq0, qa), qbit) ^ __builtin_amdgcn_alignbit(lds_ld(seq0, da + 256), lds_ld(seq0, da), dbit);
 		const uint32_t y = (x | (x >> 1)) & 0x55555555u;
-		const uint32_t r2 = min3u(scan_low(y), 32u, (uint32_t)cap2);
+		const uint32_t r2 = min3u_32(scan_low(y), (uint32_t)cap2);
 		const uint32_t nc = ((uint32_t)m3 & 0xFFFF3FFFu) + (r2 << 16);
 		const uint32_t nv = ok ? nc : kLeanDead;
 		best_key = max(best_key, (int)(nv + (uint32_t)ckd));
@@ -559,6 +576,9 @@ __device__ __forceinline__ int greedy_rows_lean(const lds_word *seq0, uint32_t l
 		if (__ballot(more) == 0ull)
 			return;
 		int q2 = (int)w >> 16; // 2 i
+		// (opaque: folded into the adds below as an SDWA operand, every +-2 k of this rare path took a register for the
+		// whole rows -- SDWA forms take no inline constant)
+		asm("" : "+v"(q2));
 		while (more) {
 			const int cap2 = min(A2, B2 + 2 * k) - (QB + q2);
 			if (cap2 <= 0)
@@ -785,7 +805,7 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 			ok = ok & ((int)((uint32_t)m3 & 0xFFFF0000u) >= thrk);
 		const uint32_t x = __builtin_amdgcn_alignbit(lds_ld(seq0, qa + 256), lds_ld(seq0, qa), qbit) ^ __builtin_amdgcn_alignbit(lds_ld(seq0, da + 256), lds_ld(seq0, da), dbit);
 		const uint32_t y = (x | (x >> 1)) & 0x55555555u;
-		const uint32_t r2 = min3u(scan_low(y), 32u, (uint32_t)cap2);
+		const uint32_t r2 = min3u_32(scan_low(y), (uint32_t)cap2);
 		// the winning parent's statistics -> this cell's (see k_gapped_diag)
 		const uint32_t w = (uint32_t)m3;
 		const uint32_t pk = (w >> 8) & 0xC0u;
@@ -816,6 +836,9 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 		if (__ballot(more) == 0ull)
 			return;
 		int q2 = (int)w >> 16; // 2 i
+		// (opaque: folded into the adds below as an SDWA operand, every +-2 k of this rare path took a register for the
+		// whole rows -- SDWA forms take no inline constant)
+		asm("" : "+v"(q2));
 		while (more) {
 			const int cap2 = min(A2, B2 + 2 * k) - (QB + q2);
 			if (cap2 <= 0)
@@ -974,7 +997,9 @@ template <int MAXL, int D> struct ListLds {
 __device__ __forceinline__ void neutral_hit(pgx_hit *hp)
 {
 	pgx_hit o = *hp;
-	o.qstart = o.qend = o.sstart = o.send = 1;
+	int one = 1;
+	asm volatile("" : "+v"(one)); // (formed here: as a constant the four words were set up at kernel entry and held -- spilled -- to this rare path)
+	o.qstart = o.qend = o.sstart = o.send = one;
 	o.score = 0;
 	o.mismatch = o.gapopen = 0;
 	*hp = o;
@@ -988,16 +1013,16 @@ __device__ __forceinline__ void list_append(bool fail, pgx_hit *hp, unsigned lon
 	const unsigned long long m = __ballot(fail);
 	if (m == 0ull)
 		return;
-	const int lane = threadIdx.x & 63, first = __ffsll((unsigned long long)m) - 1;
+	const int first = __ffsll((unsigned long long)m) - 1;
 	uint32_t base = 0;
-	if (lane == first) {
+	if ((int)lane_here() == first) {
 		base = atomicAdd(count, (uint32_t)__popcll(m));
 		if (also)
 			atomicAdd(also, (uint32_t)__popcll(m));
 	}
-	base = __shfl(base, first);
+	base = (uint32_t)__builtin_amdgcn_readlane((int)base, first); // (wave-uniform: a scalar register)
 	if (fail) {
-		const uint32_t w = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+		const uint32_t w = base + ballot_rank(m);
 		if (w < cap)
 			list[w] = (unsigned long long)(uintptr_t)hp;
 		else
@@ -1498,15 +1523,40 @@ struct Pending {
 // One round of 64 HSPs, one per lane, both sides: the record once, the letters once (right part forward, left part
 // reversed, packed behind one another in the lane's column of the transposed rows), the lean rows left then right, the
 // finished hit over the record.  HSPs this tier cannot finish wait in the two front rows (`n_pend` table slots).
+// `slot` = the HSP's place in `table`.
+// Where a side's letters lie in the lane's column follows from three small numbers: the anchor qa, the read's length L
+// and f = the anchor's offset in its 16-base database word group (the window starts D + 16 + f bases left of the read's
+// first base).  Both the staging and the side loop take the rows from here, so no offset has to outlive the rows.
+template <int MAXL, int D> struct RoundGeo {
+	using Lds = RowsLds<MAXL, D>;
+	int qa, L, awin;
+	__device__ __forceinline__ RoundGeo(int qa_, int L_, int f) : qa(qa_), L(L_), awin(qa_ + D + 16 + f) {}
+	// read letters: words wq0 .. wq1 forward from row rowR, words wr - 1 .. 0 reversed from row rowL
+	__device__ __forceinline__ int wq0() const { return qa >> 4; }
+	__device__ __forceinline__ int wq1() const { return (L + 15) >> 4; }
+	__device__ __forceinline__ int wr() const { return (qa + 15) >> 4; }
+	__device__ __forceinline__ int rowR() const { return kLeanFrontRows; }
+	__device__ __forceinline__ int rowL() const { return rowR() + (wq1() - wq0() + 1); }
+	// database letters likewise: wd0 .. wd1 from rowDR, wd - 1 .. 0 reversed from rowDL
+	__device__ __forceinline__ int wd0() const { return awin >> 4; }
+	__device__ __forceinline__ int wd1() const { return ((awin + (L - qa) + D + 16) >> 4) + 1; }
+	__device__ __forceinline__ int wd() const { return (awin + 15) >> 4; }
+	__device__ __forceinline__ int rowDR() const { return kLeanFrontRows + Lds::kQ; }
+	__device__ __forceinline__ int rowDL() const { return rowDR() + (wd1() - wd0() + 1); }
+	// bit offsets of a side's first read / database letter (side 0: left of the anchor, 1: right of it)
+	__device__ __forceinline__ int qb(int side) const { return side ? 32 * rowR() + 2 * (qa & 15) : 32 * rowL() + 2 * (16 * wr() - qa); }
+	__device__ __forceinline__ int db(int side) const { return side ? 32 * rowDR() + 2 * (awin & 15) : 32 * rowDL() + 2 * (16 * wd() - awin); }
+};
+
 template <int MAXL, int D = kGFastD>
-__device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &v, pgx_hit *__restrict__ table, pgx_hit *hp, bool mine, Pending &pend,
+__device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &v, pgx_hit *__restrict__ table, uint32_t slot, bool mine, Pending &pend,
 					  const TierLists &tl)
 {
-	using Lds = RowsLds<MAXL, D>;
-	const int lane = threadIdx.x & 63;
+	using Geo = RoundGeo<MAXL, D>;
+	const uint32_t lane4 = lane_here() * 4u;
 	const lds_word *seq0 = (const lds_word *)&lds.seq[0];
-	uint32_t *col = &lds.seq[lane]; // row r of this lane: col[r * 64]
-	const pgx_hit h = *hp;
+	uint32_t *col = &lds.seq[lane4 >> 2]; // row r of this lane: col[r * 64]
+	const pgx_hit h = table[slot];
 	const Anchor a = anchor_of(v, h);
 	bool on = mine && a.L <= MAXL;
 	// (the seed stage's own estimate of the levels a side will run, floor((2 letters - B0) / 5): a side it puts two levels
@@ -1533,7 +1583,7 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 			on = false;
 		}
 	}
-	int QB[2] = { 0, 0 }, DB0[2] = { 0, 0 };
+	const int f = awin - (a.qa + D + 16); // 0 .. 15
 	{
 		// Letters come in 16-byte loads, the same words for every lane (so they stay in registers), and go to rows that
 		// differ per lane: right of the anchor forward from the anchor's word, left of it REVERSED (words in reverse order,
@@ -1550,10 +1600,9 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 #pragma unroll
 			for (int t = 0; t < ND; t++)
 				d4[t] = *reinterpret_cast<const uint4 *>(gd + 4 * t);
-			const int wq0 = a.qa >> 4, wq1 = (a.L + 15) >> 4, wr = (a.qa + 15) >> 4;
-			const int rowR = kLeanFrontRows, rowL = rowR + (wq1 - wq0 + 1);
-			QB[1] = 32 * rowR + 2 * (a.qa & 15);
-			QB[0] = 32 * rowL + 2 * (16 * wr - a.qa);
+			const Geo g(a.qa, a.L, f);
+			const int wq0 = g.wq0(), wq1 = g.wq1(), wr = g.wr();
+			const int rowR = g.rowR(), rowL = g.rowL();
 #pragma unroll
 			for (int w = 0; w < 4 * NQ; w++) {
 				const uint32_t val = w & 2 ? (w & 1 ? q4[w >> 2].w : q4[w >> 2].z) : (w & 1 ? q4[w >> 2].y : q4[w >> 2].x);
@@ -1563,10 +1612,8 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 					col[(rowL + wr - 1 - w) * 64] = __builtin_bitreverse32(val);
 			}
 			col[(rowL + wr) * 64] = 0u; // (the window of the last letters reads one word further)
-			const int wd0 = awin >> 4, wd1 = ((awin + (a.L - a.qa) + D + 16) >> 4) + 1, wd = (awin + 15) >> 4;
-			const int rowDR = kLeanFrontRows + Lds::kQ, rowDL = rowDR + (wd1 - wd0 + 1);
-			DB0[1] = 32 * rowDR + 2 * (awin & 15);
-			DB0[0] = 32 * rowDL + 2 * (16 * wd - awin);
+			const int wd0 = g.wd0(), wd1 = g.wd1(), wd = g.wd();
+			const int rowDR = g.rowDR(), rowDL = g.rowDL();
 #pragma unroll
 			for (int w = 0; w < 4 * ND; w++) {
 				const uint32_t val = w & 2 ? (w & 1 ? d4[w >> 2].w : d4[w >> 2].z) : (w & 1 ? d4[w >> 2].y : d4[w >> 2].x);
@@ -1579,43 +1626,47 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 		}
 	}
 	lds_sync();
-	// What has to outlive the rows is kept SMALL and packed: in this kernel a spilled register is memory traffic (136 bytes
-	// of scratch per lane were ~1.3 of the 4.6 L2 misses per HSP).  Slot number, anchor | length, the record's `send` word
-	// (strand | B0 left | B0 right), the anchor's place in the subject and the subject's length, the two sides' bit offsets,
-	// the left side's result in two words.  `read` and `subject` of the record stay where they are: the hit is written
-	// over the other 24 bytes.
-	const uint32_t slot = (uint32_t)(hp - table);
-	const uint32_t geo = (uint32_t)a.qa | ((uint32_t)a.L << 10), send_w = (uint32_t)h.send;
-	const int sa = a.sa, slen = a.slen;
-	const uint32_t off_l = (uint32_t)QB[0] | ((uint32_t)DB0[0] << 16), off_r = (uint32_t)QB[1] | ((uint32_t)DB0[1] << 16);
+	// What has to outlive the rows is kept SMALL and packed: in this kernel a spilled register is memory traffic (the live
+	// scratch of all wavefronts is as large as L2).  Six words: the slot number; geo = anchor | length
+	// << 10 | f << 20 | the tier's verdict so far << 24; the record's `send` word (strand | B0 left | B0 right; once the
+	// left side is done its score takes the place of B0 left); the anchor's place in the subject and the subject's length;
+	// the left side's result.  The letters' offsets are formed again from geo in front of each side.  A lane that is not
+	// `on` keeps geo = 0: its rows are dead, and the offsets that follow from 0 lie inside its column whatever its record holds.
+	// The empty asm statements make the packed words opaque: without them the fields are unpacked once in front of the side
+	// loop and each one holds a register across the rows.
+	static_assert(MAXL <= 1023 && 2 * MAXL <= 2047, "10-bit anchor and length, an 11-bit score of a side");
+	uint32_t geo = on ? (uint32_t)a.qa | ((uint32_t)a.L << 10) | ((uint32_t)f << 20) : 0u;
+	uint32_t send_w = (uint32_t)h.send;
+	int sa = a.sa, slen = a.slen;
 	uint32_t left_pk = 0;
-	int left_s2 = 0;
-	Side rr;
-	rr.i = rr.j = rr.s2 = rr.mism = rr.gopen = 0;
-	int worst = 0; // 0 both sides done, 2 a side needs the full statistics, 1 a side is alive after D differences
+	Side rr; // a side's result: after the loop, the right side's (a copy kept beside it would live across the rows too)
+	asm volatile("" : "+v"(slot), "+v"(geo), "+v"(send_w), "+v"(sa), "+v"(slen));
 #pragma unroll 1
 	for (int side = 0; side < 2; side++) {
-		const int qa_ = (int)(geo & 1023u), L_ = (int)(geo >> 10);
-		const uint32_t off = side ? off_r : off_l;
-		Side r;
+		asm volatile("" : "+v"(geo), "+v"(send_w));
+		const int qa_ = (int)(geo & 1023u), L_ = (int)((geo >> 10) & 1023u);
+		const Geo g(qa_, L_, (int)((geo >> 20) & 15u));
 		int st;
 		if constexpr (D >= kGLag)
-			st = greedy_rows_deep<D>(seq0, (uint32_t)lane * 4u, on, (int)(off & 0xFFFFu), (int)(off >> 16), side ? L_ - qa_ : qa_,
-						 side ? slen - sa : sa, (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), r);
+			st = greedy_rows_deep<D>(seq0, lane4, on, g.qb(side), g.db(side), side ? L_ - qa_ : qa_, side ? slen - sa : sa,
+						 (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), rr);
 		else
-			st = greedy_rows_lean<D>(seq0, (uint32_t)lane * 4u, on, (int)(off & 0xFFFFu), (int)(off >> 16), side ? L_ - qa_ : qa_,
-						 side ? slen - sa : sa, (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), r);
-		worst = st == 1 || worst == 1 ? 1 : (st == 2 || worst == 2 ? 2 : 0);
-		if (side) {
-			rr = r;
-		} else {
-			left_pk = (uint32_t)r.i | ((uint32_t)r.j << 10) | ((uint32_t)r.mism << 20) | ((uint32_t)r.gopen << 26);
-			left_s2 = r.s2;
+			st = greedy_rows_lean<D>(seq0, lane4, on, g.qb(side), g.db(side), side ? L_ - qa_ : qa_, side ? slen - sa : sa,
+						 (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), rr);
+		// verdict: 0 both sides done, 2 a side needs the full statistics, 1 a side is alive after D differences
+		const uint32_t was = (geo >> 24) & 3u;
+		const uint32_t worst = st == 1 || was == 1u ? 1u : (st == 2 || was == 2u ? 2u : 0u);
+		geo = (geo & 0x00FFFFFFu) | (worst << 24);
+		if (!side) {
+			left_pk = (uint32_t)rr.i | ((uint32_t)rr.j << 10) | ((uint32_t)rr.mism << 20) | ((uint32_t)rr.gopen << 26);
+			send_w = (send_w & 0xFFFFF001u) | ((uint32_t)rr.s2 << 1);
 		}
 	}
-	if (on && worst == 0) {
-		const int qa_ = (int)(geo & 1023u), L_ = (int)(geo >> 10);
-		const int li = (int)(left_pk & 1023u), lj = (int)((left_pk >> 10) & 1023u);
+	asm volatile("" : "+v"(slot), "+v"(geo), "+v"(send_w)); // (slot: its 64-bit form for the addresses below is made here, not carried)
+	const uint32_t worst = (geo >> 24) & 3u;
+	if (on && worst == 0u) {
+		const int qa_ = (int)(geo & 1023u), L_ = (int)((geo >> 10) & 1023u);
+		const int li = (int)(left_pk & 1023u), lj = (int)((left_pk >> 10) & 1023u), left_s2 = (int)((send_w >> 1) & 0x7FFu);
 		const int bl = qa_ - li, br = qa_ + rr.i - 1, sl = sa - lj, sr = sa + rr.j - 1;
 		int4 c; // qstart, qend, sstart, send
 		if (!(send_w & 1u))
@@ -1627,7 +1678,7 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 		const uint32_t mg = ((left_pk >> 20) & 63u) + (uint32_t)rr.mism + ((((left_pk >> 26) & 63u) + (uint32_t)rr.gopen) << 16);
 		*reinterpret_cast<int2 *>(&dst->score) = make_int2((left_s2 + rr.s2) >> 1, (int)mg);
 	}
-	const bool fail_a = mine && on && worst == 2, fail_b = mine && (!on || worst == 1);
+	const bool fail_a = mine && on && worst == 2u, fail_b = mine && (!on || worst == 1u);
 	lds_sync(); // (the rows' reads are done before the letters are replaced)
 	auto park = [&](bool fail, uint32_t &n, int row, unsigned long long *list, uint32_t *count, uint32_t *also) {
 		const unsigned long long fm = __ballot(fail);
@@ -1635,12 +1686,13 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 			return;
 		const uint32_t cnt = (uint32_t)__popcll(fm);
 		if (n + cnt > 64u) { // the row is full: its slots go to the list, one atomic for all of them
-			list_append(lane < (int)n, table + (lane < (int)n ? lds.seq[row * 64 + lane] : 0u), list, count, tl.cap, also);
+			const bool have = lane_here() < n;
+			list_append(have, table + (have ? lds.seq[row * 64 + (lane4 >> 2)] : 0u), list, count, tl.cap, also);
 			n = 0;
 			lds_sync();
 		}
 		if (fail)
-			lds.seq[row * 64 + n + (uint32_t)__popcll(fm & ((1ull << lane) - 1ull))] = slot;
+			lds.seq[row * 64 + n + ballot_rank(fm)] = slot;
 		n += cnt;
 		lds_sync();
 	};
@@ -1651,9 +1703,9 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 template <int MAXL, int D = kGFastD>
 __device__ __forceinline__ void gap_flush(RowsLds<MAXL, D> &lds, pgx_hit *__restrict__ table, Pending &pend, const TierLists &tl)
 {
-	const int lane = threadIdx.x & 63;
-	list_append(lane < (int)pend.na, table + (lane < (int)pend.na ? lds.seq[lane] : 0u), tl.a, tl.a_count, tl.cap);
-	list_append(lane < (int)pend.nb, table + (lane < (int)pend.nb ? lds.seq[64 + lane] : 0u), tl.b, tl.b_count, tl.cap, tl.b_first);
+	const uint32_t lane = lane_here();
+	list_append(lane < pend.na, table + (lane < pend.na ? lds.seq[lane] : 0u), tl.a, tl.a_count, tl.cap);
+	list_append(lane < pend.nb, table + (lane < pend.nb ? lds.seq[64 + lane] : 0u), tl.b, tl.b_count, tl.cap, tl.b_first);
 	pend.na = pend.nb = 0;
 	lds_sync();
 }
@@ -1664,7 +1716,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 													  uint32_t *__restrict__ bins, TierLists tl)
 {
 	__shared__ RowsLds<MAXL, D> lds;
-	const int lane = threadIdx.x & 63;
 	const uint32_t n_items = bins[kTotalAt];
 	uint32_t *next_round = bins + kTotalAt + 1; // (zero at launch)
 	const uint32_t n_rounds = (n_items + 63u) / 64u;
@@ -1674,17 +1725,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 	// wavefront they drifted tens of regions apart and the region order bought nothing)
 	constexpr uint32_t kRoundGrab = 8;
 	for (;;) {
+		// (the grab, the round and the pending counts are wave-uniform, and `readfirstlane` says so: as a lane shuffle the
+		// grab made both loops divergent, and every value they carry sat in a vector register -- spilled -- across the rows)
 		uint32_t first = 0;
-		if (lane == 0)
+		if (lane_here() == 0u)
 			first = atomicAdd(next_round, kRoundGrab);
-		first = __shfl(first, 0);
+		first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
 		if (first >= n_rounds)
 			break;
 		const uint32_t last = first + kRoundGrab < n_rounds ? first + kRoundGrab : n_rounds;
 		for (uint32_t round = first; round < last; round++) {
-			const uint32_t idx = round * 64u + lane;
-			const bool mine = idx < n_items;
-			gap_round<MAXL, D>(lds, v, table, table + items[mine ? idx : n_items - 1u], mine, pend, tl);
+			// (a scalar base and the lane as a 32-bit offset: a 64-bit index per lane is a register pair to carry)
+			const uint32_t base = round * 64u, lane = lane_here();
+			const bool mine = base + lane < n_items;
+			const uint32_t *row = items + (size_t)base;
+			gap_round<MAXL, D>(lds, v, table, row[min(lane, n_items - 1u - base) & 63u], mine, pend, tl);
 		}
 	}
 	gap_flush<MAXL, D>(lds, table, pend, tl);
@@ -1799,7 +1854,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES))) voi
 			for (uint32_t it = 0; it < n_it; it += 64) {
 				const bool mine = it + lane < n_it;
 				const uint32_t item = __hip_atomic_load(&order[mine ? it + lane : n_it - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				gap_round<MAXL>(lds, v, table, locate(chunk + item), mine, pend, tl);
+				gap_round<MAXL>(lds, v, table, (uint32_t)(locate(chunk + item) - table), mine, pend, tl);
 			}
 		}
 		gap_flush<MAXL>(lds, table, pend, tl);
@@ -2096,7 +2151,7 @@ __device__ __forceinline__ int diag_side(const lds_word *seq0, int M, int N, Sid
 	auto lcp2 = [&](uint32_t qb, uint32_t db, uint32_t cap2) { // matching letters as bits: min(32, cap2, 2 run)
 		const uint32_t x = ld(qb) ^ ld(db);
 		const uint32_t y = (x | (x >> 1)) & 0x55555555u;
-		return min3u(scan_low(y), 32u, cap2);
+		return min3u_32(scan_low(y), cap2);
 	};
 	// ---- the first run (the same in every lane)
 	int i2 = 0;
