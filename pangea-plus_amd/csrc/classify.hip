@@ -675,7 +675,7 @@ __device__ __forceinline__ void process_candidate(const DbView &db, const uint64
 					kl = kl < 14 ? kl : 14;
 					kr = kr < 14 ? kr : 14;
 					if (L > db.deep_from) {
-						// reads the gapped stage runs with 40 differences a side (gapped.hip: greedy_rows_deep): B0 says nothing
+						// reads the gapped stage runs with 40 differences a side (gapped.hip: greedy_rows_lean<40>): B0 says nothing
 						// beyond 18 mismatches, and half the sides of a 500-base read at 7 % hold more.  Its rounds are ordered by
 						// the diagonal's own mismatch count, three levels to a step, plus the ~10 levels a side runs on past an
 						// extension that the drop-off ended inside the read

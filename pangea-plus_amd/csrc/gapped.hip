@@ -17,7 +17,7 @@
 //                  (greedy_rows_lean): the row R(d, .) of a lane in registers, letters in transposed LDS rows, one
 //                  `v_max3` per parent choice, 18 differences a side (no X-drop test is due below 19).
 //   k_gapped_rows<512, 2, 40>        reads of 321-512 bases: the same rounds with rows for 40 differences a side, the
-//                  X-drop history in a register ring (greedy_rows_deep)
+//                  X-drop history in a register ring (greedy_rows_lean's second cell format)
 //   k_gapped_pool<FLAT, ...>         the overflow table and batches of long reads: a wavefront orders a pool of HSPs by the
 //                  key byte itself, then gap_round
 //   k_gapped_list<MAXL, WAVES, 18> / <512, 2, 40>   the LISTS behind the lean tier: rows with the full statistics in
@@ -441,6 +441,14 @@ __device__ __forceinline__ bool greedy_rows(const uint32_t *rdw, const uint32_t 
 //   * the best cell is a running MAXIMUM of  score << 16 | (2047 - cell order) << 5 | G1  (first cell in (d, k) order among
 //     equal scores), one add and one max per cell; the bound is taken once per level from it (the cut never changes a
 //     result, see the header; the oracle has no cut at all).
+// The same rows hold D >= kGLag differences a side (reads of 321-512 bases: at 7 % divergence most sides of a 500-base read
+// need 19-40 levels; round 2's 40-difference tier with the per-cell statistics took 73 of the 145 ms per 1 M such reads).
+// What differs there is picked by D >= kGLag when compiling (LeanFmt and the `if constexpr (kDeep)` pieces):
+//   * the X-drop test: T[d - 19] in a 19-register ring that shifts once per level;
+//   * the cell's low 14 bits carry gap openings [5:0] | open-gap kind [7:6] | G1 [13:8] as in k_gapped_diag (with 19-40
+//     levels most best paths hold two gap columns of a kind, which the G1-only word cannot count), updated per cell;
+//   * the best cell's word is kept beside the running maximum of  score << 16 | 65535 - (d * 128 + k + 64),  so the side's
+//     statistics are read from that word and nothing is handed on for them (no status 2).
 typedef __attribute__((address_space(3))) uint32_t lds_word;
 typedef __attribute__((address_space(3))) char lds_byte;
 // (the rows' base stays a link-time constant that folds into the instruction's offset field; `off` = row * 256 | lane * 4)
@@ -459,7 +467,21 @@ constexpr int kLeanWaves = 4; // wavefronts per SIMD of the tiers for reads of <
 constexpr uint32_t kLeanDead = 0xFFF80000u; // i = -4
 constexpr uint32_t kLeanFromCur = 0x28000u;  // i + 1, priority 2 (a mismatch on this diagonal)
 constexpr uint32_t kLeanFromPrev = 0x24001u; // i + 1, priority 1, one more gap column in the subject row (from k - 1)
+constexpr uint32_t kDeepFromPrev = 0x24100u; // the same with G1 at bit 8
 constexpr int kLeanFrontRows = 2;            // spare rows in front of a lane's letters
+
+// The two cell formats of greedy_rows_lean, side by side:       D < kGLag (G1 only)   D >= kGLag (full statistics)
+template <int D> struct LeanFmt {
+	static constexpr bool kDeep = D >= kGLag;
+	static constexpr uint32_t kStartLow = kDeep ? 0x80u : 0u;               // the first run's word: nothing | open-gap kind "none"
+	static constexpr uint32_t kFromPrev = kDeep ? kDeepFromPrev : kLeanFromPrev;
+	// order of a cell = d << kOrdBits | (k + half of that stride), the first run's: d = k = 0; the best cell's key =
+	// score << 16 | (kOrdTop - order) << kOrdShift | (G1 below the shift)
+	static constexpr int kOrdBits = kDeep ? 7 : 6;                          // d * 64 + k + 32   | d * 128 + k + 64
+	static constexpr int kOrdTop = kDeep ? 65535 : 2047;
+	static constexpr int kOrdShift = kDeep ? 0 : 5;                         // G1 in 5 bits      | (G1 in the kept word)
+	static constexpr int kMaxD = kDeep ? 61 : 31;                           // 5-bit fields      | 6-bit fields
+};
 
 // matching letters from bit offsets qb / db of the lane's staged letters on, as BITS (2 per letter): min(32, cap2, 2 run)
 __device__ __forceinline__ uint32_t lean_lcp(const lds_word *seq0, uint32_t lane4, uint32_t qb, uint32_t db, uint32_t cap2)
@@ -470,13 +492,16 @@ __device__ __forceinline__ uint32_t lean_lcp(const lds_word *seq0, uint32_t lane
 	return min3u_32(scan_low(y), cap2);
 }
 
-// status: 0 done, 1 cells alive after D differences (next tier), 2 the best cell holds two or more gap columns of a kind (next tier)
+// status: 0 done, 1 cells alive after D differences (next tier), 2 the best cell holds two or more gap columns of a kind
+// (next tier; D < kGLag only, whose word does not count the openings)
 // seq0 = the letter rows (row r of lane l at byte r * 256 + l * 4), lane4 = l * 4; QB / DB0 = bit offsets of the side's first read / database
 // letter there; M, N = letters of the read / of the subject on the side; b0 as for greedy_rows
 template <int D>
 __device__ __forceinline__ int greedy_rows_lean(const lds_word *seq0, uint32_t lane4, bool on, int QB, int DB0, int M, int N, int b0, Side &out)
 {
-	static_assert(D < kGLag && D < 32, "no X-drop history, 5-bit fields");
+	using Fmt = LeanFmt<D>;
+	constexpr bool kDeep = Fmt::kDeep; // the X-drop history and the full statistics are kept
+	static_assert(D <= Fmt::kMaxD, "a level and a diagonal fit the order's fields");
 	constexpr int kCells = 2 * D + 3, C = D + 1;
 	const int A2 = 2 * M + QB, B2 = 2 * N + QB; // ends of the two sequences as read bit offsets (B2 + 2 k on diagonal k)
 	// ---- the first run
@@ -500,250 +525,13 @@ __device__ __forceinline__ int greedy_rows_lean(const lds_word *seq0, uint32_t l
 #pragma unroll
 	for (int c = 0; c < kCells; c++)
 		R[c] = kLeanDead;
-	R[C] = live ? (uint32_t)i2 << 16 : kLeanDead;
-	// order of a cell: d * 64 + k + 32 (the first run: 32); key = s2 << 16 | (2047 - order) << 5 | G1
-	int best_key = (i2 << 16) | ((2047 - 32) << 5);
-	const uint32_t Qc = (uint32_t)QB << 16;
-	const uint32_t D0 = (uint32_t)(DB0 - QB) << 16;
-	const uint32_t c17 = 0x20000u;
-	uint32_t prev = kLeanDead;
-	// per level, per lane: the diagonals k the bound lets live are lo1 .. lo1 + width (none: lo1 = 1 << 20)
-	int lo1 = 0;
-	uint32_t width = 0;
-	uint32_t alldead = 0xFFFFFFFFu; // AND of the level's new cells: negative while every one of them is dead
-	auto set_range = [&](int d) { // for level d, from the best score so far
-		const int best = max(best_key >> 16, b0 - 1);
-		const int lo = 6 * d - (2 * N - best) + 1, hi = (2 * M - best) - 6 * d - 1; // lo <= k <= hi
-		const bool some = lo <= hi;
-		lo1 = some ? lo : (1 << 20);
-		width = some ? (uint32_t)(hi - lo) : 0u;
-		return some && lo <= d && hi >= -d;
+	R[C] = live ? ((uint32_t)i2 << 16) | Fmt::kStartLow : kLeanDead;
+	auto ckd_of = [](int d, int k) { // -(k + 6 d) << 16 | the order's part of a key (see LeanFmt)
+		return (int)((uint32_t)(-(k + 6 * d)) << 16) | ((Fmt::kOrdTop - ((d << Fmt::kOrdBits) + k + (1 << (Fmt::kOrdBits - 1)))) << Fmt::kOrdShift);
 	};
-	// running per-cell values of a level (k ascending): Dk = D0 - k << 17, Bk = B2 + 2 k, rk = k - lo1
-	uint32_t Dk = 0, rk = 0;
-	int Bk = 0;
-	auto level_start = [&](int d) {
-		Dk = D0 + ((uint32_t)d << 17);
-		Bk = B2 - 2 * d;
-		rk = (uint32_t)(-d - lo1);
-		prev = kLeanDead;
-		alldead = 0xFFFFFFFFu;
-	};
-	// one cell; c compile-time; ckd = -(k + 6 d) << 16 | (2047 - order) << 5, wave-uniform
-	auto cell = [&](auto cc, auto reach_c, int ckd, uint32_t &r2_out) {
-		constexpr int c = decltype(cc)::value;
-		constexpr int k = c - C;
-		constexpr int reach = decltype(reach_c)::value;
-		const uint32_t cur = R[c], nxt = R[c + 1];
-		int m3;
-		if constexpr (k < -reach)
-			m3 = (int)nxt; // the left edge of the level: only diagonal k + 1 can lead here
-		else if constexpr (k > reach)
-			m3 = (int)(prev + kLeanFromPrev); // the right edge: only diagonal k - 1
-		else if constexpr (k - 1 < -reach && k + 1 > reach)
-			m3 = (int)(cur + kLeanFromCur); // level 1, k = 0
-		else if constexpr (k - 1 < -reach)
-			m3 = max((int)(cur + kLeanFromCur), (int)nxt);
-		else if constexpr (k + 1 > reach)
-			m3 = max((int)(cur + kLeanFromCur), (int)(prev + kLeanFromPrev));
-		else
-			m3 = max((int)(cur + kLeanFromCur), max((int)(prev + kLeanFromPrev), (int)nxt));
-		const uint32_t t = (uint32_t)m3 + Qc, u = t + Dk;
-		const uint32_t qbit = (uint32_t)((int)t >> 16), dbit = (uint32_t)((int)u >> 16);
-		const uint32_t qa = ((t >> 13) & 0xFFFFFF00u) | lane4, da = ((u >> 13) & 0xFFFFFF00u) | lane4;
-		const int cap2 = min(A2, Bk) - (int)qbit;
-		const bool ok = ((m3 | cap2) >= 0) & (rk <= width);
-		const uint32_t x = __builtin_amdgcn_alignbit(lds_ld(seq0, qa + 256), lds_ld(seq0, qa), qbit) ^ __builtin_amdgcn_alignbit(lds_ld(seq0, da + 256), lds_ld(seq0, da), dbit);
-		const uint32_t y = (x | (x >> 1)) & 0x55555555u;
-		const uint32_t r2 = min3u_32(scan_low(y), (uint32_t)cap2);
-		const uint32_t nc = ((uint32_t)m3 & 0xFFFF3FFFu) + (r2 << 16);
-		const uint32_t nv = ok ? nc : kLeanDead;
-		best_key = max(best_key, (int)(nv + (uint32_t)ckd));
-		alldead &= nv;
-		r2_out = r2;
-		prev = cur;
-		R[c] = nv;
-		Dk -= c17;
-		Bk += 2;
-		rk += 1u;
-	};
-	// a cell whose first 16 letters all matched and that has more to compare: slide on (rare off the alignment's own diagonal)
-	auto slide_on = [&](auto cc, int ckd, uint32_t r2) {
-		constexpr int c = decltype(cc)::value;
-		constexpr int k = c - C;
-		const uint32_t w = R[c];
-		bool more = (int)w >= 0 && r2 == 32u;
-		if (__ballot(more) == 0ull)
-			return;
-		int q2 = (int)w >> 16; // 2 i
-		// (opaque: folded into the adds below as an SDWA operand, every +-2 k of this rare path took a register for the
-		// whole rows -- SDWA forms take no inline constant)
-		asm("" : "+v"(q2));
-		while (more) {
-			const int cap2 = min(A2, B2 + 2 * k) - (QB + q2);
-			if (cap2 <= 0)
-				break;
-			const uint32_t rr = lean_lcp(seq0, lane4, (uint32_t)(QB + q2), (uint32_t)(DB0 + q2 - 2 * k), (uint32_t)cap2);
-			q2 += (int)rr;
-			more = rr == 32u;
-		}
-		const uint32_t nv = (int)w >= 0 ? ((uint32_t)q2 << 16) | (w & 0xFFFFu) : w;
-		R[c] = nv;
-		best_key = max(best_key, (int)(nv + (uint32_t)ckd));
-	};
-	// cells c0 .. c0 + n - 1 are dead for every lane: written so, the running values stepped past them
-	auto skip_group = [&](auto c0c, auto nc) {
-		constexpr int c0 = decltype(c0c)::value, n = decltype(nc)::value;
-		prev = R[c0 + n - 1];
-		static_for<0, n>([&](auto jc) { R[c0 + decltype(jc)::value] = kLeanDead; });
-		Dk -= c17 * (uint32_t)n;
-		Bk += 2 * n;
-		rk += (uint32_t)n;
-	};
-	auto ckd_of = [](int d, int k) { return (int)((uint32_t)(-(k + 6 * d)) << 16) | ((2047 - (d * 64 + k + 32)) << 5); };
-	bool done = false, over = false;
-	bool in_range = set_range(1);
-	live = live && in_range;
-	static_for<1, kGUnrollLevels + 1>([&](auto dc) {
-		constexpr int d = decltype(dc)::value;
-		if (!done) {
-			if (__ballot(live) == 0ull) {
-				done = true;
-			} else {
-				level_start(d);
-				// groups of cells: straight code, then the (rare) longer slides of the group; a group no lane's bound lets
-				// live (the dead half of a side's last levels) is written dead without looking
-				static_for<0, (2 * d + 1 + kLeanGroup - 1) / kLeanGroup>([&](auto gc) {
-					constexpr int c0 = C - d + kLeanGroup * decltype(gc)::value;
-					constexpr int n = (C + d + 1 - c0) < kLeanGroup ? (C + d + 1 - c0) : kLeanGroup;
-					if (__ballot(lo1 <= c0 + n - 1 - C && lo1 + (int)width >= c0 - C) == 0ull) {
-						skip_group(std::integral_constant<int, c0>{}, std::integral_constant<int, n>{});
-					} else {
-						uint32_t r2[kLeanGroup] = {};
-						uint32_t any32 = 0;
-						static_for<0, n>([&](auto jc) {
-							constexpr int c = c0 + decltype(jc)::value;
-							cell(std::integral_constant<int, c>{}, std::integral_constant<int, d - 1>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							any32 |= r2[decltype(jc)::value];
-						});
-						if (__ballot((any32 & 32u) != 0u) != 0ull) {
-							static_for<0, n>([&](auto jc) {
-								constexpr int c = c0 + decltype(jc)::value;
-								slide_on(std::integral_constant<int, c>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							});
-						}
-					}
-				});
-				const bool some = set_range(d + 1);
-				live = (int)alldead >= 0 && some;
-			}
-		}
-	});
-	for (int d = kGUnrollLevels + 1; !done && __ballot(live) != 0ull; d++) {
-		if (d > D) {
-			over = live;
-			break;
-		}
-		level_start(d);
-		// (the running values start at k = -d: cells left of it are skipped without a step)
-		static_for<0, (kCells - 2 + kLeanGroup - 1) / kLeanGroup>([&](auto gc) {
-			constexpr int c0 = 1 + decltype(gc)::value * kLeanGroup;
-			constexpr int n = (kCells - 1 - c0) < kLeanGroup ? (kCells - 1 - c0) : kLeanGroup;
-			if (!(c0 + n - 1 - C < -d || c0 - C > d)) {
-				if (c0 - C >= -d && c0 + n - 1 - C <= d) {
-					// the whole group lies inside the level: the same straight code as above
-					if (__ballot(lo1 <= c0 + n - 1 - C && lo1 + (int)width >= c0 - C) == 0ull) {
-						skip_group(std::integral_constant<int, c0>{}, std::integral_constant<int, n>{});
-					} else {
-						uint32_t r2[kLeanGroup] = {};
-						uint32_t any32 = 0;
-						static_for<0, n>([&](auto jc) {
-							constexpr int c = c0 + decltype(jc)::value;
-							cell(std::integral_constant<int, c>{}, std::integral_constant<int, D>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							any32 |= r2[decltype(jc)::value];
-						});
-						if (__ballot((any32 & 32u) != 0u) != 0ull) {
-							static_for<0, n>([&](auto jc) {
-								constexpr int c = c0 + decltype(jc)::value;
-								slide_on(std::integral_constant<int, c>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							});
-						}
-					}
-				} else {
-					// a group the level's ends cut through: cell by cell
-					static_for<0, n>([&](auto jc) {
-						constexpr int c = c0 + decltype(jc)::value;
-						constexpr int k = c - C;
-						if (!(k < -d || k > d)) {
-							uint32_t r2 = 0;
-							cell(std::integral_constant<int, c>{}, std::integral_constant<int, D>{}, ckd_of(d, k), r2);
-							if (__ballot((r2 & 32u) != 0u) != 0ull)
-								slide_on(std::integral_constant<int, c>{}, ckd_of(d, k), r2);
-						}
-					});
-				}
-			}
-		});
-		const bool some = set_range(d + 1);
-		live = (int)alldead >= 0 && some;
-	}
-	// the best cell: score, where, its gap columns
-	const int s2 = best_key >> 16;
-	const int order = 2047 - ((best_key >> 5) & 2047);
-	const int bd = order >> 6, bk = (order & 63) - 32;
-	const int g1 = best_key & 31, g2 = g1 - bk;
-	out.i = (s2 + bk + 6 * bd) >> 1;
-	out.j = out.i - bk;
-	out.s2 = s2;
-	out.gopen = g1 + g2;
-	out.mism = bd - (g1 + g2);
-	if (over)
-		return 1;
-	// (a gap column in the subject row and one in the query row are two gaps; only two columns of one kind can be one gap or two)
-	return g1 >= 2 || g2 >= 2 ? 2 : 0;
-}
-
-// The lean rows for D >= kGLag differences a side (reads of 320-512 bases: at 7 % divergence most sides of a 500-base read
-// need 19-40 levels; round 2's 40-difference tier with the per-cell statistics took 73 of the 145 ms per 1 M such reads).
-// Differences to greedy_rows_lean: the X-drop test (T[d - 19] in a 19-register ring that shifts once per level); the
-// cell's low 14 bits carry gap openings [5:0] | open-gap kind [7:6] | G1 [13:8] as in k_gapped_diag (with 19-40 levels
-// most best paths hold two gap columns of a kind, which the G1-only word cannot count), the best cell's word is kept
-// beside the running maximum of  score << 16 | 65535 - (d * 128 + k + 64).
-// status: 0 done, 1 cells alive after D differences (next tier)
-// seq0 = the letter rows (row r of lane l at byte r * 256 + l * 4), lane4 = l * 4; QB / DB0 = bit offsets of the side's first read / database
-// letter there; M, N = letters of the read / of the subject on the side; b0 as for greedy_rows
-constexpr uint32_t kDeepFromPrev = 0x24100u; // i + 1, priority 1, G1 + 1 (G1 at bit 8)
-template <int D>
-__device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t lane4, bool on, int QB, int DB0, int M, int N, int b0, Side &out)
-{
-	static_assert(D >= kGLag && D < 62, "X-drop history kept, 6-bit fields");
-	constexpr int kCells = 2 * D + 3, C = D + 1;
-	const int A2 = 2 * M + QB, B2 = 2 * N + QB; // ends of the two sequences as read bit offsets (B2 + 2 k on diagonal k)
-	// ---- the first run
-	int i2 = 0; // 2 i
-	if (on) {
-		for (;;) {
-			const int cap2 = min(2 * M, 2 * N) - i2;
-			if (cap2 <= 0)
-				break;
-			const uint32_t r2 = lean_lcp(seq0, lane4, (uint32_t)(QB + i2), (uint32_t)(DB0 + i2), (uint32_t)cap2);
-			i2 += (int)r2;
-			if (r2 < 32u)
-				break;
-		}
-	}
-	out.i = out.j = i2 >> 1;
-	out.s2 = i2;
-	out.mism = out.gopen = 0;
-	bool live = on && !(i2 == 2 * M || i2 == 2 * N);
-	uint32_t R[kCells];
-#pragma unroll
-	for (int c = 0; c < kCells; c++)
-		R[c] = kLeanDead;
-	R[C] = live ? ((uint32_t)i2 << 16) | 0x80u : kLeanDead;
-	// order of a cell: d * 128 + k + 64 (the first run: 64); key = s2 << 16 | 65535 - order
-	int best_key = (i2 << 16) | (65535 - 64);
-	uint32_t best_word = ((uint32_t)i2 << 16) | 0x80u;
+	int best_key = (i2 << 16) | (ckd_of(0, 0) & 0xFFFF);
+	// kDeep only (without it these stay unused and cost nothing):
+	uint32_t best_word = ((uint32_t)i2 << 16) | Fmt::kStartLow; // the best cell's word
 	int Tr[kGLag]; // T[d - 19 .. d - 1] while level d runs (T[x] = best score within x differences; x < 0: no test)
 #pragma unroll
 	for (int x = 0; x < kGLag; x++)
@@ -775,9 +563,20 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 		rk = (uint32_t)(-d - lo1);
 		prev = kLeanDead;
 		alldead = 0xFFFFFFFFu;
-		thrk = (int)((uint32_t)(Tr[0] - kGX2 + 6 * d - d) << 16);
+		if constexpr (kDeep)
+			thrk = (int)((uint32_t)(Tr[0] - kGX2 + 6 * d - d) << 16);
 	};
-	// one cell; c compile-time; ckd = -(k + 6 d) << 16 | (2047 - order) << 5, wave-uniform
+	// a new or longer cell against the best one (the first in (d, k) order among equal scores stays)
+	auto note_best = [&](uint32_t nv, int ckd) {
+		if constexpr (kDeep) {
+			const int key = (int)((nv & 0xFFFF0000u) + (uint32_t)ckd);
+			best_word = key > best_key ? nv : best_word;
+			best_key = max(best_key, key);
+		} else {
+			best_key = max(best_key, (int)(nv + (uint32_t)ckd)); // (G1 in the key's low bits)
+		}
+	};
+	// one cell; c compile-time; ckd = ckd_of(d, k), wave-uniform
 	auto cell = [&](auto cc, auto reach_c, int ckd, uint32_t &r2_out) {
 		constexpr int c = decltype(cc)::value;
 		constexpr int k = c - C;
@@ -787,37 +586,38 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 		if constexpr (k < -reach)
 			m3 = (int)nxt; // the left edge of the level: only diagonal k + 1 can lead here
 		else if constexpr (k > reach)
-			m3 = (int)(prev + kDeepFromPrev); // the right edge: only diagonal k - 1
+			m3 = (int)(prev + Fmt::kFromPrev); // the right edge: only diagonal k - 1
 		else if constexpr (k - 1 < -reach && k + 1 > reach)
 			m3 = (int)(cur + kLeanFromCur); // level 1, k = 0
 		else if constexpr (k - 1 < -reach)
 			m3 = max((int)(cur + kLeanFromCur), (int)nxt);
 		else if constexpr (k + 1 > reach)
-			m3 = max((int)(cur + kLeanFromCur), (int)(prev + kDeepFromPrev));
+			m3 = max((int)(cur + kLeanFromCur), (int)(prev + Fmt::kFromPrev));
 		else
-			m3 = max((int)(cur + kLeanFromCur), max((int)(prev + kDeepFromPrev), (int)nxt));
+			m3 = max((int)(cur + kLeanFromCur), max((int)(prev + Fmt::kFromPrev), (int)nxt));
 		const uint32_t t = (uint32_t)m3 + Qc, u = t + Dk;
 		const uint32_t qbit = (uint32_t)((int)t >> 16), dbit = (uint32_t)((int)u >> 16);
 		const uint32_t qa = ((t >> 13) & 0xFFFFFF00u) | lane4, da = ((u >> 13) & 0xFFFFFF00u) | lane4;
 		const int cap2 = min(A2, Bk) - (int)qbit;
 		bool ok = ((m3 | cap2) >= 0) & (rk <= width);
-		if constexpr (reach >= kGLag - 1) // (levels below kGLag pass every X-drop test)
+		if constexpr (kDeep && reach >= kGLag - 1) // (levels below kGLag pass every X-drop test)
 			ok = ok & ((int)((uint32_t)m3 & 0xFFFF0000u) >= thrk);
 		const uint32_t x = __builtin_amdgcn_alignbit(lds_ld(seq0, qa + 256), lds_ld(seq0, qa), qbit) ^ __builtin_amdgcn_alignbit(lds_ld(seq0, da + 256), lds_ld(seq0, da), dbit);
 		const uint32_t y = (x | (x >> 1)) & 0x55555555u;
 		const uint32_t r2 = min3u_32(scan_low(y), (uint32_t)cap2);
-		// the winning parent's statistics -> this cell's (see k_gapped_diag)
 		const uint32_t w = (uint32_t)m3;
-		const uint32_t pk = (w >> 8) & 0xC0u;
-		const uint32_t differs = ((w ^ pk) & 0xC0u) != 0u ? 1u : 0u;
-		const uint32_t inc = (w & 0x8000u) ? 0u : differs;
-		const uint32_t nc = ((w & 0xFFFF0000u) + (r2 << 16)) | (((w & 0x3F3Fu) + inc) | (r2 != 0u ? 0x80u : pk));
-		const uint32_t nv = ok ? nc : kLeanDead;
-		{
-			const int key = (int)((nv & 0xFFFF0000u) + (uint32_t)ckd);
-			best_word = key > best_key ? nv : best_word;
-			best_key = max(best_key, key);
+		uint32_t nc;
+		if constexpr (kDeep) {
+			// the winning parent's statistics -> this cell's (see k_gapped_diag)
+			const uint32_t pk = (w >> 8) & 0xC0u;
+			const uint32_t differs = ((w ^ pk) & 0xC0u) != 0u ? 1u : 0u;
+			const uint32_t inc = (w & 0x8000u) ? 0u : differs;
+			nc = ((w & 0xFFFF0000u) + (r2 << 16)) | (((w & 0x3F3Fu) + inc) | (r2 != 0u ? 0x80u : pk));
+		} else {
+			nc = (w & 0xFFFF3FFFu) + (r2 << 16);
 		}
+		const uint32_t nv = ok ? nc : kLeanDead;
+		note_best(nv, ckd);
 		alldead &= nv;
 		r2_out = r2;
 		prev = cur;
@@ -825,7 +625,8 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 		Dk -= c17;
 		Bk += 2;
 		rk += 1u;
-		thrk += 0x10000;
+		if constexpr (kDeep)
+			thrk += 0x10000;
 	};
 	// a cell whose first 16 letters all matched and that has more to compare: slide on (rare off the alignment's own diagonal)
 	auto slide_on = [&](auto cc, int ckd, uint32_t r2) {
@@ -849,11 +650,7 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 		}
 		const uint32_t nv = (int)w >= 0 ? ((uint32_t)q2 << 16) | (w & 0xFFFFu) : w;
 		R[c] = nv;
-		{
-			const int key = (int)((nv & 0xFFFF0000u) + (uint32_t)ckd);
-			best_word = key > best_key ? nv : best_word;
-			best_key = max(best_key, key);
-		}
+		note_best(nv, ckd);
 	};
 	// cells c0 .. c0 + n - 1 are dead for every lane: written so, the running values stepped past them
 	auto skip_group = [&](auto c0c, auto nc) {
@@ -863,14 +660,39 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 		Dk -= c17 * (uint32_t)n;
 		Bk += 2 * n;
 		rk += (uint32_t)n;
-		thrk += 0x10000 * n;
+		if constexpr (kDeep)
+			thrk += 0x10000 * n;
 	};
-	auto ckd_of = [](int d, int k) { return (int)((uint32_t)(-(k + 6 * d)) << 16) | (65535 - (d * 128 + k + 64)); };
-	auto level_end = [&]() { // T[d] = the best score so far; the ring moves on
+	// cells c0 .. c0 + n - 1, all inside level d: straight code, then the (rare) longer slides of the group; a group no
+	// lane's bound lets live (the dead half of a side's last levels) is written dead without looking
+	auto group = [&](auto c0c, auto nc, auto reach_c, int d) {
+		constexpr int c0 = decltype(c0c)::value, n = decltype(nc)::value;
+		if (__ballot(lo1 <= c0 + n - 1 - C && lo1 + (int)width >= c0 - C) == 0ull) {
+			skip_group(c0c, nc);
+		} else {
+			uint32_t r2[kLeanGroup] = {};
+			uint32_t any32 = 0;
+			static_for<0, n>([&](auto jc) {
+				constexpr int c = c0 + decltype(jc)::value;
+				cell(std::integral_constant<int, c>{}, reach_c, ckd_of(d, c - C), r2[decltype(jc)::value]);
+				any32 |= r2[decltype(jc)::value];
+			});
+			if (__ballot((any32 & 32u) != 0u) != 0ull) {
+				static_for<0, n>([&](auto jc) {
+					constexpr int c = c0 + decltype(jc)::value;
+					slide_on(std::integral_constant<int, c>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
+				});
+			}
+		}
+	};
+	auto level_end = [&](bool some) { // the level's verdict; T[d] = the best score so far, the ring moves on
+		live = (int)alldead >= 0 && some;
+		if constexpr (kDeep) {
 #pragma unroll
-		for (int x = 0; x + 1 < kGLag; x++)
-			Tr[x] = Tr[x + 1];
-		Tr[kGLag - 1] = best_key >> 16;
+			for (int x = 0; x + 1 < kGLag; x++)
+				Tr[x] = Tr[x + 1];
+			Tr[kGLag - 1] = best_key >> 16;
+		}
 	};
 	bool done = false, over = false;
 	bool in_range = set_range(1);
@@ -882,32 +704,12 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 				done = true;
 			} else {
 				level_start(d);
-				// groups of cells: straight code, then the (rare) longer slides of the group; a group no lane's bound lets
-				// live (the dead half of a side's last levels) is written dead without looking
 				static_for<0, (2 * d + 1 + kLeanGroup - 1) / kLeanGroup>([&](auto gc) {
 					constexpr int c0 = C - d + kLeanGroup * decltype(gc)::value;
 					constexpr int n = (C + d + 1 - c0) < kLeanGroup ? (C + d + 1 - c0) : kLeanGroup;
-					if (__ballot(lo1 <= c0 + n - 1 - C && lo1 + (int)width >= c0 - C) == 0ull) {
-						skip_group(std::integral_constant<int, c0>{}, std::integral_constant<int, n>{});
-					} else {
-						uint32_t r2[kLeanGroup] = {};
-						uint32_t any32 = 0;
-						static_for<0, n>([&](auto jc) {
-							constexpr int c = c0 + decltype(jc)::value;
-							cell(std::integral_constant<int, c>{}, std::integral_constant<int, d - 1>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							any32 |= r2[decltype(jc)::value];
-						});
-						if (__ballot((any32 & 32u) != 0u) != 0ull) {
-							static_for<0, n>([&](auto jc) {
-								constexpr int c = c0 + decltype(jc)::value;
-								slide_on(std::integral_constant<int, c>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							});
-						}
-					}
+					group(std::integral_constant<int, c0>{}, std::integral_constant<int, n>{}, std::integral_constant<int, d - 1>{}, d);
 				});
-				const bool some = set_range(d + 1);
-				live = (int)alldead >= 0 && some;
-				level_end();
+				level_end(set_range(d + 1));
 			}
 		}
 	});
@@ -924,23 +726,7 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 			if (!(c0 + n - 1 - C < -d || c0 - C > d)) {
 				if (c0 - C >= -d && c0 + n - 1 - C <= d) {
 					// the whole group lies inside the level: the same straight code as above
-					if (__ballot(lo1 <= c0 + n - 1 - C && lo1 + (int)width >= c0 - C) == 0ull) {
-						skip_group(std::integral_constant<int, c0>{}, std::integral_constant<int, n>{});
-					} else {
-						uint32_t r2[kLeanGroup] = {};
-						uint32_t any32 = 0;
-						static_for<0, n>([&](auto jc) {
-							constexpr int c = c0 + decltype(jc)::value;
-							cell(std::integral_constant<int, c>{}, std::integral_constant<int, D>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							any32 |= r2[decltype(jc)::value];
-						});
-						if (__ballot((any32 & 32u) != 0u) != 0ull) {
-							static_for<0, n>([&](auto jc) {
-								constexpr int c = c0 + decltype(jc)::value;
-								slide_on(std::integral_constant<int, c>{}, ckd_of(d, c - C), r2[decltype(jc)::value]);
-							});
-						}
-					}
+					group(std::integral_constant<int, c0>{}, std::integral_constant<int, n>{}, std::integral_constant<int, D>{}, d);
 				} else {
 					// a group the level's ends cut through: cell by cell
 					static_for<0, n>([&](auto jc) {
@@ -956,21 +742,30 @@ __device__ __forceinline__ int greedy_rows_deep(const lds_word *seq0, uint32_t l
 				}
 			}
 		});
-		const bool some = set_range(d + 1);
-		live = (int)alldead >= 0 && some;
-		level_end();
+		level_end(set_range(d + 1));
 	}
-	// the best cell: score, where, its statistics
+	// the best cell: score, where, its gap columns and openings
 	const int s2 = best_key >> 16;
-	const int order = 65535 - (best_key & 65535);
-	const int bd = order >> 7, bk = (order & 127) - 64;
-	const int g1 = (int)((best_word >> 8) & 63u), g2 = g1 - bk;
+	const int order = Fmt::kOrdTop - ((best_key >> Fmt::kOrdShift) & Fmt::kOrdTop);
+	const int bd = order >> Fmt::kOrdBits, bk = (order & ((1 << Fmt::kOrdBits) - 1)) - (1 << (Fmt::kOrdBits - 1));
+	int g1, gopen;
+	if constexpr (kDeep) {
+		g1 = (int)((best_word >> 8) & 63u);
+		gopen = (int)(best_word & 63u);
+	} else {
+		g1 = best_key & 31;
+		gopen = g1 + (g1 - bk); // (the openings are the gap columns while there is at most one of each kind: status 2 below otherwise)
+	}
+	const int g2 = g1 - bk; // gap columns in the query row
 	out.i = (s2 + bk + 6 * bd) >> 1;
 	out.j = out.i - bk;
 	out.s2 = s2;
-	out.gopen = (int)(best_word & 63u);
+	out.gopen = gopen;
 	out.mism = bd - (g1 + g2);
-	return over ? 1 : 0;
+	if (over)
+		return 1;
+	// (a gap column in the subject row and one in the query row are two gaps; only two columns of one kind can be one gap or two)
+	return !kDeep && (g1 >= 2 || g2 >= 2) ? 2 : 0;
 }
 
 constexpr int kBlkItems = 2048; // HSPs a wavefront orders at a time
@@ -1646,13 +1441,8 @@ __device__ __forceinline__ void gap_round(RowsLds<MAXL, D> &lds, const GapView &
 		asm volatile("" : "+v"(geo), "+v"(send_w));
 		const int qa_ = (int)(geo & 1023u), L_ = (int)((geo >> 10) & 1023u);
 		const Geo g(qa_, L_, (int)((geo >> 20) & 15u));
-		int st;
-		if constexpr (D >= kGLag)
-			st = greedy_rows_deep<D>(seq0, lane4, on, g.qb(side), g.db(side), side ? L_ - qa_ : qa_, side ? slen - sa : sa,
-						 (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), rr);
-		else
-			st = greedy_rows_lean<D>(seq0, lane4, on, g.qb(side), g.db(side), side ? L_ - qa_ : qa_, side ? slen - sa : sa,
-						 (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), rr);
+		const int st = greedy_rows_lean<D>(seq0, lane4, on, g.qb(side), g.db(side), side ? L_ - qa_ : qa_, side ? slen - sa : sa,
+						   (int)(side ? (send_w >> 12) & 0x7FFu : (send_w >> 1) & 0x7FFu), rr);
 		// verdict: 0 both sides done, 2 a side needs the full statistics, 1 a side is alive after D differences
 		const uint32_t was = (geo >> 24) & 3u;
 		const uint32_t worst = st == 1 || was == 1u ? 1u : (st == 2 || was == 2u ? 2u : 0u);
