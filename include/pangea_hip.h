@@ -388,6 +388,19 @@ typedef struct {
 } pgx_trim_opts;
 enum { PGX_TRIM_NONE = 0, PGX_TRIM_FASTQ = 1, PGX_TRIM_QSEQ = 2, PGX_TRIM_UNKNOWN = 3, PGX_TRIM_FASTA_QUAL = 4, PGX_TRIM_FASTA_JOIN = 5 };
 int pgx_trim_file(const pgx_trim_opts *o, char **log_text, char **fasta_text, size_t *fasta_len, int *mode);
+/* The same run handed straight to Classify: `out` is the batch that pgx_reads_from_fasta_text(fasta_text, fasta_len, 0, -1)
+ * makes of pgx_trim_file's fasta_text -- same reads, names, ambiguity words, DUST bits, search classes and pieces -- without
+ * the FASTA text crossing to the host and back; log_text, mode and the status are pgx_trim_file's.
+ *   out    NULL where pgx_trim_file leaves fasta_text NULL (usage, unopenable file); the empty batch where the script leaves
+ *          an empty file (format not recognised, PGX_TRIM_FASTA_QUAL); closed with pgx_reads_close
+ *   route  how the batch was made.  PGX_TRIM_ROUTE_PACKED: FASTQ / QSEQ records whose letters and names were written from
+ *          the raw lines into the batch's tables, no FASTA text formed.  PGX_TRIM_ROUTE_TEXT: the FASTA text was written
+ *          into HBM and split there -- PGX_TRIM_FASTA_JOIN, the empty file, and every call with a record the splitter would
+ *          read differently from what was printed (a sequence line beginning with '>', a line end inside a kept span, a
+ *          carriage return in a header or a kept span) or with 2^32 letters or name bytes and more.  PGX_TRIM_ROUTE_NONE:
+ *          no batch.  Both routes give the same batch. */
+enum { PGX_TRIM_ROUTE_NONE = 0, PGX_TRIM_ROUTE_PACKED = 1, PGX_TRIM_ROUTE_TEXT = 2 };
+int pgx_trim_reads(const pgx_trim_opts *o, char **log_text, pgx_reads **out, int *mode, int *route);
 
 /* diagnostics (tools/probe_gather.py): 64-byte lines per second the device delivers to random 8-byte lane loads over a
  * table of `table_bytes` — the access shape of the seed stage's index and database fetches, i.e. the roof that stage

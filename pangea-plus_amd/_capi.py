@@ -97,7 +97,7 @@ SYMBOLS = [
     "pgx_reads_get", "pgx_reads_get_dust", "pgx_db_get_dust", "pgx_blast_search", "pgx_hits_close", "pgx_hits_count", "pgx_hits_copy",
     "pgx_hits_read_offsets", "pgx_hits_read_counts", "pgx_hits_slice", "pgx_hits_format", "pgx_db_bind_taxonomy", "pgx_db_subject_lineage",
     "pgx_rdp_from_file", "pgx_rdp_from_synth", "pgx_rdp_close", "pgx_consensus_batch", "pgx_classify_consensus", "pgx_classify_consensus_tri", "pgx_vote3_batch", "pgx_vote3_format",
-    "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_trim_file", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
+    "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_trim_file", "pgx_trim_reads", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
 ]
 
 
@@ -145,6 +145,7 @@ def _declare(L):
     sig("pgx_megaclust_batch", C.c_int, [V, V, V, V, I64, V, V, V, V])
     sig("pgx_megaclustable", C.c_int, [C.c_int, V, V])
     sig("pgx_trim_file", C.c_int, [V, V, V, V, V])
+    sig("pgx_trim_reads", C.c_int, [V, V, V, V, V])
     sig("pgx_probe_gather", C.c_int, [C.c_uint64, C.c_int, V, V])
     sig("pgx_probe_issue", C.c_int, [C.c_int, C.c_int, V])
     sig("pgx_blast_score_columns", C.c_int, [C.c_int32, I64, I64, I64, C.c_char_p, C.c_char_p])
@@ -336,6 +337,19 @@ class Reads(_Handle):
         p = C.c_void_p()
         _check(lib().pgx_reads_from_fasta_text(text, len(text), first, count, C.byref(p)))
         return cls(p)
+
+    @classmethod
+    def from_trim(cls, a, b=None, g=None, t=None, q=None, j=False):
+        """trim2() handed straight to Classify: the batch `from_fasta_text` makes of the FASTA trim2(a, ...) returns, built in
+        HBM without that text.  Returns (reads, messages, mode, route): reads is None where trim2 returns no FASTA (usage,
+        unopenable file); route is TRIM_ROUTE_PACKED when the letters and names went from the raw lines into the batch,
+        TRIM_ROUTE_TEXT when the FASTA was written in HBM and split there (same batch either way)."""
+        opts = _trim_opts(a, b, g, t, q, j)
+        log, p, mode, route = C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        rc = lib().pgx_trim_reads(C.byref(opts), C.byref(log), C.byref(p), C.byref(mode), C.byref(route))
+        messages = _take_text(log.value)
+        _check(rc)
+        return (cls(p) if p.value else None), messages, mode.value, route.value
 
     def write_fasta(self, path):
         _check(lib().pgx_reads_write_fasta(self.ptr, _b(path)))
@@ -609,6 +623,12 @@ class _TrimOpts(C.Structure):
 
 
 TRIM_NONE, TRIM_FASTQ, TRIM_QSEQ, TRIM_UNKNOWN, TRIM_FASTA_QUAL, TRIM_FASTA_JOIN = 0, 1, 2, 3, 4, 5
+TRIM_ROUTE_NONE, TRIM_ROUTE_PACKED, TRIM_ROUTE_TEXT = 0, 1, 2
+
+
+def _trim_opts(a, b, g, t, q, j):
+    txt = lambda v: None if v is None else str(v).encode()  # noqa: E731  option texts, as on the command line
+    return _TrimOpts(_b(a), _b(b), txt(g), txt(t), txt(q), 1 if j else 0)
 
 
 def trim2(a, b=None, g=None, t=None, q=None, j=False):
@@ -616,8 +636,7 @@ def trim2(a, b=None, g=None, t=None, q=None, j=False):
     input.  Returns (messages, runblast FASTA bytes or None, mode): the script writes the FASTA to
     output_files/trim2/<basename of a>_runblast.fasta, which is left to the caller (bin/trim2 does it); its stdout is
     the FASTA followed by the messages when mode == TRIM_FASTQ, the messages alone otherwise."""
-    txt = lambda v: None if v is None else str(v).encode()  # noqa: E731  option texts, as on the command line
-    opts = _TrimOpts(_b(a), _b(b), txt(g), txt(t), txt(q), 1 if j else 0)
+    opts = _trim_opts(a, b, g, t, q, j)
     log, fasta, ln, mode = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_int()
     rc = lib().pgx_trim_file(C.byref(opts), C.byref(log), C.byref(fasta), C.byref(ln), C.byref(mode))
     messages = _take_text(log.value)

@@ -199,6 +199,24 @@ int reads_from_fasta_text(std::shared_ptr<const TextBlob> text, int64_t first, i
 			  std::vector<uint32_t> *amb_count, std::unique_ptr<pgx_reads> &out);
 int db_build_index(pgx_db *db);
 int choose_index_bits(int64_t n_postings);
+// The records of a FASTA text, split and resident: what the device splitter leaves and what the second half of the import
+// (packing, pieces, DUST, classes) takes.  Texts under 4 GiB only: the offsets are 32-bit.
+struct DeviceFasta {
+	DevBuf<unsigned char> d_letters; // the letters of all records back to back (16 bytes of padding behind them)
+	std::vector<uint32_t> let_off; // n_rec + 1 letter offsets
+	// the names (first word of each header) behind one another, gathered on the device while the text is there: n_rec + 1
+	// offsets and the bytes, on the device and on the host.  The batch keeps THESE, not the file: round 3 kept the file
+	// mapped for the batch's life and read names from it on demand (a file rewritten in place changed them)
+	DevBuf<unsigned char> d_names;
+	DevBuf<uint32_t> d_name_at;
+	std::vector<uint32_t> name_at;
+	std::string names;
+};
+constexpr uint64_t kDeviceSplitLimit = (1ull << 32) - 2; // FASTA texts from this size on take the host splitter
+int fasta_split_resident(const unsigned char *d_text, size_t n_bytes, DeviceFasta &out);
+int reads_from_device_fasta(DeviceFasta &df, int64_t first, int64_t count, bool fold_to_g, std::vector<uint32_t> *amb_count,
+			    std::unique_ptr<pgx_reads> &out);
+int reads_from_resident_fasta_text(const unsigned char *d_text, size_t n_bytes, std::unique_ptr<pgx_reads> &out);
 
 // trim.hip
 int device_line_index(const uint8_t *d_text, uint64_t n, bool open_tail, DevBuf<uint64_t> &start, uint64_t *n_lines_out);

@@ -946,18 +946,6 @@ __global__ void k_fa_copy_letters(const unsigned char *__restrict__ text, const 
 	       [](uint8_t c) { return c; });
 }
 
-struct DeviceFasta {
-	DevBuf<unsigned char> d_letters;
-	std::vector<uint32_t> let_off; // n_rec + 1 letter offsets
-	// the names (first word of each header) behind one another, gathered on the device while the text is there: n_rec + 1
-	// offsets and the bytes, on the device and on the host.  The batch keeps THESE, not the file: round 3 kept the file
-	// mapped for the batch's life and read names from it on demand (a file rewritten in place changed them)
-	DevBuf<unsigned char> d_names;
-	DevBuf<uint32_t> d_name_at;
-	std::vector<uint32_t> name_at;
-	std::string names;
-};
-
 // names of the records into one blob: one lane per record (a name is a handful of bytes)
 __global__ void k_fa_gather_names(const unsigned char *__restrict__ text, const uint32_t *__restrict__ rec_name_off,
 				  const uint32_t *__restrict__ name_at, uint32_t n_rec, unsigned char *__restrict__ names)
@@ -986,21 +974,24 @@ static int u32_scan(const uint32_t *in, uint32_t *out, size_t n, bool inclusive)
 	return 0;
 }
 
-static int fasta_split_device(const char *text, size_t n_bytes, DeviceFasta &out)
+// records of FASTA text that lies in HBM (n_bytes < 4 GiB - 2, the 16 bytes behind it readable: the kernels read aligned
+// 16-byte words)
+int fasta_split_resident(const unsigned char *d_text, size_t n_bytes, DeviceFasta &out)
 {
 	const uint32_t n = (uint32_t)n_bytes;
 	out.let_off.assign(1, 0);
-	if (n == 0)
+	out.name_at.assign(1, 0);
+	out.names.clear();
+	if (n == 0) {
+		PGX_TRY(out.d_names.alloc(1, 0, 16));
 		return out.d_letters.alloc(1, 0, 16);
-	DevBuf<unsigned char> d_text;
+	}
 	DevBuf<uint8_t> d_flag;
 	DevBuf<uint32_t> d_idx;
-	PGX_TRY(d_text.alloc(n, 0, 16)); // + padding: the kernels read aligned 16-byte words
-	PGX_TRY(d_text.upload((const unsigned char *)text, n));
 	PGX_TRY(d_flag.alloc(n));
 	PGX_TRY(d_idx.alloc(n));
 	const unsigned gb = (n + 255) / 256;
-	hipLaunchKernelGGL(k_fa_line_flags, dim3(gb), dim3(256), 0, 0, d_text.data(), n, d_flag.data());
+	hipLaunchKernelGGL(k_fa_line_flags, dim3(gb), dim3(256), 0, 0, d_text, n, d_flag.data());
 	{
 		size_t bytes = 0;
 		PGX_HIP(rocprim::exclusive_scan(nullptr, bytes, d_flag.data(), d_idx.data(), 0u, (size_t)n, rocprim::plus<uint32_t>()));
@@ -1025,7 +1016,7 @@ static int fasta_split_device(const char *text, size_t n_bytes, DeviceFasta &out
 	d_flag.release();
 	d_idx.release();
 	const unsigned gl = (n_lines + 255) / 256;
-	hipLaunchKernelGGL(k_fa_line_info, dim3(gl), dim3(256), 0, 0, d_text.data(), d_line_start.data(), n_lines, d_hdr.data(),
+	hipLaunchKernelGGL(k_fa_line_info, dim3(gl), dim3(256), 0, 0, d_text, d_line_start.data(), n_lines, d_hdr.data(),
 			   d_nlet.data(), d_name_len.data());
 	PGX_HIP(hipGetLastError());
 	PGX_TRY(u32_scan(d_hdr.data(), d_rec_incl.data(), (size_t)n_lines + 1, true));
@@ -1039,7 +1030,7 @@ static int fasta_split_device(const char *text, size_t n_bytes, DeviceFasta &out
 	PGX_TRY(d_rno.alloc((size_t)n_rec + 1));
 	PGX_TRY(d_rnl.alloc((size_t)n_rec + 1));
 	PGX_TRY(out.d_letters.alloc(n_let ? n_let : 1, 0, 16));
-	hipLaunchKernelGGL(k_fa_copy_letters, dim3((unsigned)(((uint64_t)n_lines * kGroup + 255) / 256)), dim3(256), 0, 0, d_text.data(), d_line_start.data(), d_hdr.data(), d_nlet.data(),
+	hipLaunchKernelGGL(k_fa_copy_letters, dim3((unsigned)(((uint64_t)n_lines * kGroup + 255) / 256)), dim3(256), 0, 0, d_text, d_line_start.data(), d_hdr.data(), d_nlet.data(),
 			   d_let_off.data(), d_rec_incl.data(), d_name_len.data(), n_lines, out.d_letters.data(), d_rlo.data(), d_rno.data(),
 			   d_rnl.data());
 	PGX_HIP(hipGetLastError());
@@ -1055,13 +1046,22 @@ static int fasta_split_device(const char *text, size_t n_bytes, DeviceFasta &out
 	const uint32_t n_name_bytes = out.name_at[n_rec];
 	PGX_TRY(out.d_names.alloc(n_name_bytes ? n_name_bytes : 1, 0, 16));
 	if (n_rec)
-		hipLaunchKernelGGL(k_fa_gather_names, dim3((n_rec + 255) / 256), dim3(256), 0, 0, d_text.data(), d_rno.data(), out.d_name_at.data(), n_rec,
+		hipLaunchKernelGGL(k_fa_gather_names, dim3((n_rec + 255) / 256), dim3(256), 0, 0, d_text, d_rno.data(), out.d_name_at.data(), n_rec,
 				   out.d_names.data());
 	PGX_HIP(hipGetLastError());
 	out.names.resize(n_name_bytes);
 	if (n_name_bytes)
 		PGX_TRY(out.d_names.download((unsigned char *)&out.names[0], n_name_bytes));
 	return 0;
+}
+
+// the same for text in host memory: uploaded as it is
+static int fasta_split_device(const char *text, size_t n_bytes, DeviceFasta &out)
+{
+	DevBuf<unsigned char> d_text;
+	PGX_TRY(d_text.alloc(n_bytes, 0, 16)); // + padding: the kernels read aligned 16-byte words
+	PGX_TRY(d_text.upload((const unsigned char *)text, n_bytes));
+	return fasta_split_resident(d_text.data(), n_bytes, out);
 }
 
 // ------------------------------------------------------------------------------------------ pieces of reads with long N runs
@@ -1248,90 +1248,49 @@ int reads_from_fasta_ex(const char *path, int64_t first, int64_t count, bool fol
 	return reads_from_fasta_text(std::move(text), first, count, fold_to_g, amb_count, out);
 }
 
-// the same for FASTA text already in memory (pgx_blastn_run streams large query files through this in pieces)
-int reads_from_fasta_text(std::shared_ptr<const TextBlob> text_ptr, int64_t first, int64_t count, bool fold_to_g,
-			  std::vector<uint32_t> *amb_count, std::unique_ptr<pgx_reads> &out)
+// when a FASTA import started and when its records were found (the PGX_TRACE line of the import)
+struct ImportTimes {
+	std::chrono::steady_clock::time_point t_read, t_split;
+};
+
+// records [first, first + count) of `total`, clamped as the importers do
+static void clamp_window(int64_t total, int64_t &first, int64_t &count)
 {
-	const TextBlob &text = *text_ptr;
-	PGX_TRY(require_device());
-	const bool trace = getenv("PGX_TRACE") != nullptr;
-	auto now = [] { return std::chrono::steady_clock::now(); };
-	auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-		return std::chrono::duration<double, std::milli>(b - a).count();
-	};
-	const auto t_read = now();
-	// records, letters and names: found on the device for files under 4 GiB, by the host splitter otherwise
-	DeviceFasta df;
-	std::vector<uint64_t> rec_off; // n_rec + 1 letter offsets
-	std::unique_ptr<pgx_reads> rd(new pgx_reads());
-	FastaLetters fl;
-	const bool on_device = text.size() < (1ull << 32) - 2;
-	if (on_device) {
-		PGX_TRY(fasta_split_device(text.data(), text.size(), df));
-		rec_off.assign(df.let_off.begin(), df.let_off.end());
-	} else {
-		split_fasta_text(std::string(text.data(), text.size()), fl); // (4 GiB and more: the host splitter works on a string)
-		rec_off = fl.off;
-	}
-	const auto t_split = now();
-	int64_t total = (int64_t)rec_off.size() - 1;
 	if (first < 0)
 		first = 0;
 	if (first > total)
 		first = total;
 	if (count < 0 || first + count > total)
 		count = total - first;
-	rd->n = count;
-	rd->first = first;
+}
+
+// lengths, word offsets and the longest read of a batch of `rd->n` reads; length_of(i) = letters of read i
+template <typename F> static void reads_place(pgx_reads *rd, F length_of)
+{
+	const int64_t count = rd->n;
 	rd->h_len.resize((size_t)count);
 	rd->h_woff.resize((size_t)count + 1);
 	uint64_t nw = 0;
-	rd->name_off.resize((size_t)count);
-	rd->name_len.resize((size_t)count);
-	std::string own_names; // host splitter: names are copied out of the header strings
 	for (int64_t i = 0; i < count; i++) {
-		uint64_t L = rec_off[(size_t)(first + i) + 1] - rec_off[(size_t)(first + i)];
+		const uint64_t L = length_of(i);
 		rd->h_len[(size_t)i] = (uint32_t)L;
 		nw = place_read_words(nw, (L + 31) / 32);
 		rd->h_woff[(size_t)i] = (uint32_t)nw;
 		nw += (L + 31) / 32;
 		if ((int32_t)L > rd->max_len)
 			rd->max_len = (int32_t)L;
-		if (on_device) {
-			rd->name_off[(size_t)i] = df.name_at[(size_t)(first + i)] - df.name_at[(size_t)first];
-			rd->name_len[(size_t)i] = df.name_at[(size_t)(first + i) + 1] - df.name_at[(size_t)(first + i)];
-		} else {
-			const std::string nm = first_word(fl.headers[(size_t)(first + i)]);
-			rd->name_off[(size_t)i] = own_names.size();
-			rd->name_len[(size_t)i] = (uint32_t)nm.size();
-			own_names += nm;
-		}
 	}
 	rd->h_woff[(size_t)count] = (uint32_t)nw;
 	rd->n_words = (int64_t)nw;
-	// letters of the selected block are packed by a kernel
-	const uint64_t l0 = rec_off[(size_t)first], l1 = rec_off[(size_t)(first + count)];
-	std::vector<uint64_t> loff((size_t)count + 1);
-	for (int64_t i = 0; i <= count; i++)
-		loff[(size_t)i] = rec_off[(size_t)(first + i)] - l0;
-	DevBuf<unsigned char> d_letters_host;
-	const unsigned char *d_letters_ptr = nullptr;
-	if (on_device) {
-		d_letters_ptr = df.d_letters.data() + l0;
-		// the batch's own copy of its names (host and device); the file's text is let go when this call returns
-		const uint32_t nb0 = df.name_at[(size_t)first], nb1 = df.name_at[(size_t)(first + count)];
-		rd->h_text = std::make_shared<const TextBlob>(df.names.substr(nb0, nb1 - nb0));
-		PGX_TRY(rd->d_names.alloc(nb1 - nb0 ? nb1 - nb0 : 1, 0, 16));
-		if (nb1 > nb0 && hipMemcpy(rd->d_names.data(), df.d_names.data() + nb0, nb1 - nb0, hipMemcpyDeviceToDevice) != hipSuccess)
-			return fail(PGX_E_NODEVICE, "copy of the read names failed");
-	} else {
-		rd->h_text = std::make_shared<const TextBlob>(std::move(own_names));
-		PGX_TRY(rd->d_names.alloc(rd->h_text->size() ? rd->h_text->size() : 1, 0, 16));
-		PGX_TRY(rd->d_names.upload((const unsigned char *)rd->h_text->data(), rd->h_text->size()));
-		PGX_TRY(d_letters_host.alloc(l1 - l0 ? l1 - l0 : 1, 0, 16));
-		PGX_TRY(d_letters_host.upload((const unsigned char *)fl.letters.data() + l0, l1 - l0));
-		d_letters_ptr = d_letters_host.data();
-	}
+}
+
+// The second half of a FASTA import: `rd` has its lengths, word offsets and names; the letters of its reads lie in HBM at
+// d_letters + loff[i].  Packs both strands, finds the pieces of reads with long N runs, runs DUST and builds the classes.
+static int reads_pack(std::unique_ptr<pgx_reads> &rd, const unsigned char *d_letters_ptr, const std::vector<uint64_t> &loff, bool fold_to_g,
+		      std::vector<uint32_t> *amb_count, const ImportTimes &tm, std::unique_ptr<pgx_reads> &out)
+{
+	const int64_t count = rd->n;
+	const uint64_t nw = (uint64_t)rd->n_words;
 	std::vector<uint32_t> at((size_t)count + 1, 0);
 	for (int64_t i = 0; i < count; i++)
 		at[(size_t)i + 1] = at[(size_t)i] + rd->name_len[(size_t)i];
@@ -1377,15 +1336,114 @@ int reads_from_fasta_text(std::shared_ptr<const TextBlob> text_ptr, int64_t firs
 	}
 	if (rd->has_amb && getenv("PGX_NO_PIECES") == nullptr)
 		PGX_TRY(reads_build_pieces(rd.get(), d_letters_ptr, d_loff.data(), d_namb.data()));
-	const auto t_pack = now();
+	const auto t_pack = std::chrono::steady_clock::now();
 	PGX_TRY(reads_finish(rd.get()));
-	if (trace) {
+	if (getenv("PGX_TRACE") != nullptr) {
+		auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+			return std::chrono::duration<double, std::milli>(b - a).count();
+		};
 		(void)hipDeviceSynchronize();
-		fprintf(stderr, "[pgx trace] reads_from_fasta: split %.1f ms, tables+pack %.1f ms, strands %.1f ms\n", ms(t_read, t_split),
-			ms(t_split, t_pack), ms(t_pack, now()));
+		fprintf(stderr, "[pgx trace] reads_from_fasta: split %.1f ms, tables+pack %.1f ms, strands %.1f ms\n", ms(tm.t_read, tm.t_split),
+			ms(tm.t_split, t_pack), ms(t_pack, std::chrono::steady_clock::now()));
 	}
 	out = std::move(rd);
 	return 0;
+}
+
+static int reads_from_device_fasta_at(DeviceFasta &df, int64_t first, int64_t count, bool fold_to_g, std::vector<uint32_t> *amb_count,
+				      const ImportTimes &tm, std::unique_ptr<pgx_reads> &out)
+{
+	std::unique_ptr<pgx_reads> rd(new pgx_reads());
+	clamp_window((int64_t)df.let_off.size() - 1, first, count);
+	rd->n = count;
+	rd->first = first;
+	reads_place(rd.get(), [&](int64_t i) { return (uint64_t)(df.let_off[(size_t)(first + i) + 1] - df.let_off[(size_t)(first + i)]); });
+	rd->name_off.resize((size_t)count);
+	rd->name_len.resize((size_t)count);
+	for (int64_t i = 0; i < count; i++) {
+		rd->name_off[(size_t)i] = df.name_at[(size_t)(first + i)] - df.name_at[(size_t)first];
+		rd->name_len[(size_t)i] = df.name_at[(size_t)(first + i) + 1] - df.name_at[(size_t)(first + i)];
+	}
+	// letters of the selected block are packed by a kernel
+	const uint64_t l0 = df.let_off[(size_t)first];
+	std::vector<uint64_t> loff((size_t)count + 1);
+	for (int64_t i = 0; i <= count; i++)
+		loff[(size_t)i] = df.let_off[(size_t)(first + i)] - l0;
+	// the batch's own copy of its names (host and device); the file's text is let go when this call returns
+	const uint32_t nb0 = df.name_at[(size_t)first], nb1 = df.name_at[(size_t)(first + count)];
+	rd->h_text = std::make_shared<const TextBlob>(df.names.substr(nb0, nb1 - nb0));
+	PGX_TRY(rd->d_names.alloc(nb1 - nb0 ? nb1 - nb0 : 1, 0, 16));
+	if (nb1 > nb0 && hipMemcpy(rd->d_names.data(), df.d_names.data() + nb0, nb1 - nb0, hipMemcpyDeviceToDevice) != hipSuccess)
+		return fail(PGX_E_NODEVICE, "copy of the read names failed");
+	return reads_pack(rd, df.d_letters.data() + l0, loff, fold_to_g, amb_count, tm, out);
+}
+
+// A batch from records that already lie split in HBM (letters, letter offsets, names): what reads_from_fasta_text does once
+// the splitter has run, and where pgx_trim_reads hands over the records its kernels wrote (trim.hip).
+int reads_from_device_fasta(DeviceFasta &df, int64_t first, int64_t count, bool fold_to_g, std::vector<uint32_t> *amb_count,
+			    std::unique_ptr<pgx_reads> &out)
+{
+	PGX_TRY(require_device());
+	const auto t = std::chrono::steady_clock::now();
+	return reads_from_device_fasta_at(df, first, count, fold_to_g, amb_count, ImportTimes{ t, t }, out);
+}
+
+// ... and from FASTA text that lies in HBM (n_bytes < 4 GiB - 2; 16 bytes behind it are readable)
+int reads_from_resident_fasta_text(const unsigned char *d_text, size_t n_bytes, std::unique_ptr<pgx_reads> &out)
+{
+	PGX_TRY(require_device());
+	ImportTimes tm;
+	tm.t_read = std::chrono::steady_clock::now();
+	DeviceFasta df;
+	PGX_TRY(fasta_split_resident(d_text, n_bytes, df));
+	tm.t_split = std::chrono::steady_clock::now();
+	return reads_from_device_fasta_at(df, 0, -1, false, nullptr, tm, out);
+}
+
+// the same for FASTA text already in memory (pgx_blastn_run streams large query files through this in pieces)
+int reads_from_fasta_text(std::shared_ptr<const TextBlob> text_ptr, int64_t first, int64_t count, bool fold_to_g,
+			  std::vector<uint32_t> *amb_count, std::unique_ptr<pgx_reads> &out)
+{
+	const TextBlob &text = *text_ptr;
+	PGX_TRY(require_device());
+	ImportTimes tm;
+	tm.t_read = std::chrono::steady_clock::now();
+	// records, letters and names: found on the device for files under 4 GiB, by the host splitter otherwise
+	if (text.size() < kDeviceSplitLimit) {
+		DeviceFasta df;
+		PGX_TRY(fasta_split_device(text.data(), text.size(), df));
+		tm.t_split = std::chrono::steady_clock::now();
+		return reads_from_device_fasta_at(df, first, count, fold_to_g, amb_count, tm, out);
+	}
+	FastaLetters fl;
+	split_fasta_text(std::string(text.data(), text.size()), fl); // (4 GiB and more: the host splitter works on a string)
+	tm.t_split = std::chrono::steady_clock::now();
+	const std::vector<uint64_t> &rec_off = fl.off; // n_rec + 1 letter offsets
+	std::unique_ptr<pgx_reads> rd(new pgx_reads());
+	clamp_window((int64_t)rec_off.size() - 1, first, count);
+	rd->n = count;
+	rd->first = first;
+	reads_place(rd.get(), [&](int64_t i) { return rec_off[(size_t)(first + i) + 1] - rec_off[(size_t)(first + i)]; });
+	rd->name_off.resize((size_t)count);
+	rd->name_len.resize((size_t)count);
+	std::string own_names; // names are copied out of the header strings
+	for (int64_t i = 0; i < count; i++) {
+		const std::string nm = first_word(fl.headers[(size_t)(first + i)]);
+		rd->name_off[(size_t)i] = own_names.size();
+		rd->name_len[(size_t)i] = (uint32_t)nm.size();
+		own_names += nm;
+	}
+	const uint64_t l0 = rec_off[(size_t)first], l1 = rec_off[(size_t)(first + count)];
+	std::vector<uint64_t> loff((size_t)count + 1);
+	for (int64_t i = 0; i <= count; i++)
+		loff[(size_t)i] = rec_off[(size_t)(first + i)] - l0;
+	rd->h_text = std::make_shared<const TextBlob>(std::move(own_names));
+	PGX_TRY(rd->d_names.alloc(rd->h_text->size() ? rd->h_text->size() : 1, 0, 16));
+	PGX_TRY(rd->d_names.upload((const unsigned char *)rd->h_text->data(), rd->h_text->size()));
+	DevBuf<unsigned char> d_letters_host;
+	PGX_TRY(d_letters_host.alloc(l1 - l0 ? l1 - l0 : 1, 0, 16));
+	PGX_TRY(d_letters_host.upload((const unsigned char *)fl.letters.data() + l0, l1 - l0));
+	return reads_pack(rd, d_letters_host.data(), loff, fold_to_g, amb_count, tm, out);
 }
 
 // a database whose ambiguity codes read as G (SOAP mode), built from a file database

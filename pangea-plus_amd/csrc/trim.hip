@@ -15,6 +15,12 @@
 // files read line by line in step; the host numifies the quality fields, as it does the score columns of megaclust2; the
 // running sum, the start/end carried from record to record and the printed text are the device's), `-j -b` = join_fasta.
 // Not covered: a negative -t.
+//
+// pgx_trim_reads (the end of this file) is the same run handed to Classify without the FASTA text: the measure kernels also
+// count each record's letters and name bytes as the FASTA splitter (seqdb.hip) would find them, two more scans give the
+// offsets, and k_fq_pack / k_qs_pack write the compact letters and the names straight from the raw lines (the packed route).
+// A call with a record whose text the splitter would read differently (below: "regular") writes the FASTA into HBM as
+// before and lets the splitter read it there (the text route).
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
@@ -168,15 +174,36 @@ struct FqRec {
 	uint32_t keep1, keep2; // bytes of substr($sequence, 0, $end), or kZeroRead
 };
 
+// What the measure kernels report in `flags`, and the columns they fill for the packed route (PACK = true).
+// A record is REGULAR when the FASTA splitter (k_fa_line_info, k_fa_copy_letters) would read its text back as one record
+// with exactly the letters and the name counted here.  It is not when
+//   * its sequence line would begin with '>' (the splitter takes that line for a header),
+//   * a kept span holds a '\n' (FASTQ second mate whose quality line is longer than its sequence line),
+//   * its header or a kept span holds a '\r'.  The splitter drops one '\r' at the end of a line and keeps every other; the
+//     rule here is wider than that on purpose: any '\r' that would be printed sends the call to the text route.
+// Blanks and tabs of a kept span are no letters (the splitter drops them); the name is the header's first word.
+// Every record's first line is its header, so nothing precedes the first header; a QSEQ pair that prints nothing is
+// regular, it is simply absent.
+constexpr uint32_t kFlagTooLong = 1u, kFlagIrregular = 2u;
+constexpr uint32_t kNameFull = 0x80000000u; // name_take: the header has no blank, so the pad colons and ":AB" belong to the name
+struct PackCols {
+	uint64_t *n_let, *n_name; // per input record (+ one 0): letters and name bytes, the inputs of the two scans
+	uint32_t *name_take;      // raw header bytes the name is made of | kNameFull
+	uint32_t *printed;        // QSEQ: 1 when the pair prints (+ one 0), the input of the rank scan
+};
+
 // one lane per output record: 4 lines, or 8 with -b (mates interleaved in the -a file, trim2.4.pl:492-495)
+template <bool PACK>
 __global__ __launch_bounds__(256) void k_fq_measure(TextView t, uint64_t n_rec, int paired, uint64_t gap, FqRec *__restrict__ rec,
-						    uint64_t *__restrict__ out_len, uint32_t *__restrict__ too_long)
+						    uint64_t *__restrict__ out_len, uint32_t *__restrict__ flags, PackCols pk)
 {
 	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r > n_rec)
 		return;
 	if (r == n_rec) {
 		out_len[r] = 0;
+		if constexpr (PACK)
+			pk.n_let[r] = pk.n_name[r] = 0;
 		return;
 	}
 	const uint64_t l0 = r * (paired ? 8 : 4);
@@ -184,7 +211,24 @@ __global__ __launch_bounds__(256) void k_fq_measure(TextView t, uint64_t n_rec, 
 	if (hdr.n && t.text[hdr.off + hdr.n - 1] == '\n')
 		hdr.n--; // chomp($header1)
 	uint64_t len = 1 + 4 + 1; // '>' ":AB\n" "\n"
-	for_bytes(t.text, hdr.off, hdr.n, [&](uint8_t c, uint64_t) { len += c != '@'; }); // s/@//g
+	// PACK: the name ends at the header's first blank or tab, else behind ":AB"; `lead` = the first byte of the sequence line
+	uint64_t name = 0, take = hdr.n, let = 0;
+	bool blank = false, odd = hdr.n >= 0x7FFFFFFFull;
+	int lead = -1;
+	for_bytes(t.text, hdr.off, hdr.n, [&](uint8_t c, uint64_t i) { // s/@//g
+		len += c != '@';
+		if constexpr (PACK) {
+			odd |= c == '\r';
+			if (!blank) {
+				if (c == ' ' || c == '\t') {
+					blank = true;
+					take = i;
+				} else {
+					name += c != '@';
+				}
+			}
+		}
+	});
 	FqRec f = { kZeroRead, kZeroRead };
 	bool bad = false;
 	for (int mate = 0; mate < (paired ? 2 : 1); mate++) {
@@ -192,25 +236,62 @@ __global__ __launch_bounds__(256) void k_fq_measure(TextView t, uint64_t n_rec, 
 		bad |= seq.n >= 0x7FFFFFFFull;
 		const uint64_t end = quality_end(t.text, qual.off, qual.n, 33);
 		const uint64_t kept = end < seq.n ? end : seq.n;
+		if constexpr (PACK)
+			if (mate == 1) { // the N's between the mates
+				if (lead < 0 && gap)
+					lead = 'N';
+				let += gap;
+			}
 		if (kept >= kLengthCutoff && !bad) {
 			if (mate == 0) {
 				f.keep1 = (uint32_t)kept;
 				// $fastq1 =~ s/\s//g (also the tab of :571)
-				for_bytes(t.text, seq.off, kept, [&](uint8_t c, uint64_t) { len += !p_space_dev(c); });
+				for_bytes(t.text, seq.off, kept, [&](uint8_t c, uint64_t) {
+					const bool k = !p_space_dev(c);
+					len += k;
+					if constexpr (PACK)
+						if (k) {
+							if (lead < 0)
+								lead = c;
+							let++;
+						}
+				});
 			} else {
 				f.keep2 = (uint32_t)kept;
 				len += kept + 1; // the second mate keeps its tab (:571, :508)
+				if constexpr (PACK) {
+					for_bytes(t.text, seq.off, kept, [&](uint8_t c, uint64_t) {
+						odd |= c == '\n' || c == '\r';
+						if (lead < 0)
+							lead = c;
+						let += c != ' ' && c != '\t';
+					});
+					if (lead < 0)
+						lead = '\t';
+				}
 			}
 		} else {
 			len += 1; // "0"
+			if constexpr (PACK) {
+				if (lead < 0)
+					lead = '0';
+				let++;
+			}
 		}
 	}
 	if (paired)
 		len += gap;
 	if (bad)
-		atomicOr(too_long, 1u);
+		atomicOr(flags, kFlagTooLong);
 	rec[r] = f;
 	out_len[r] = len;
+	if constexpr (PACK) {
+		if (odd || lead == '>')
+			atomicOr(flags, kFlagIrregular);
+		pk.n_let[r] = let;
+		pk.n_name[r] = name + (blank ? 0 : 3);
+		pk.name_take[r] = (uint32_t)take | (blank ? 0u : kNameFull);
+	}
 }
 
 // the FASTA text of record `r`, written by one lane group (trim2.4.pl:487-515)
@@ -247,6 +328,44 @@ __global__ __launch_bounds__(256) void k_fq_emit(TextView t, uint64_t n_rec, int
 	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
 	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r < n_rec; r += groups)
 		fq_emit_record(t, r, paired, gap, rec[r], out_off[r], out);
+}
+
+// The packed route's writer: what fq_emit_record prints, as the splitter would read it back -- the letters of record r (no
+// blanks, no tabs) at let_off[r], the first word of its header at name_at[r] -- and the two offsets as the 32-bit entries
+// of a DeviceFasta.  One lane group per record; group n_rec writes the closing offsets.
+__global__ __launch_bounds__(256) void k_fq_pack(TextView t, uint64_t n_rec, int paired, uint64_t gap, const FqRec *__restrict__ rec,
+						 const uint32_t *__restrict__ name_take, const uint64_t *__restrict__ let_off,
+						 const uint64_t *__restrict__ name_at, char *__restrict__ letters, char *__restrict__ names,
+						 uint32_t *__restrict__ let_off32, uint32_t *__restrict__ name_at32)
+{
+	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
+	auto same = [](uint8_t c) { return c; };
+	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r <= n_rec; r += groups) {
+		uint64_t pos = let_off[r], npos = name_at[r];
+		if ((threadIdx.x & (kGroup - 1)) == 0) {
+			let_off32[r] = (uint32_t)pos;
+			name_at32[r] = (uint32_t)npos;
+		}
+		if (r == n_rec)
+			break;
+		const uint64_t l0 = r * (paired ? 8 : 4);
+		const FqRec f = rec[r];
+		const uint32_t take = name_take[r];
+		w_copy(names, npos, t.text + line_of(t, l0).off, take & ~kNameFull, [](uint8_t c) { return c != '@'; }, same);
+		if (take & kNameFull)
+			w_lit(names, npos, ":AB", 3);
+		if (f.keep1 != kZeroRead)
+			w_copy(letters, pos, t.text + line_of(t, l0 + 1).off, f.keep1, [](uint8_t c) { return !p_space_dev(c); }, same);
+		else
+			w_lit(letters, pos, "0", 1);
+		if (paired) {
+			w_fill(letters, pos, 'N', gap);
+			if (f.keep2 != kZeroRead)
+				w_copy(letters, pos, t.text + line_of(t, l0 + 5).off, f.keep2, [](uint8_t c) { return c != ' ' && c != '\t'; }, same);
+			else
+				w_lit(letters, pos, "0", 1);
+		}
+	}
 }
 
 // ------------------------------------------------------------------------------------------------- QSEQ
@@ -323,14 +442,19 @@ __device__ bool qs_trim(const uint8_t *__restrict__ text, Span seq, Span qual, l
 __device__ __forceinline__ bool span_is(const uint8_t *__restrict__ text, Span s, char c) { return s.n == 1 && text[s.off] == (uint8_t)c; }
 
 // one lane per line of file A and the line of the same number of file B (trim2.4.pl:180-246)
+template <bool PACK>
 __global__ __launch_bounds__(256) void k_qs_measure(TextView a, TextView b, uint64_t n_rec, uint64_t gap, long long t1, long long t2,
-						    QsRec *__restrict__ rec, uint64_t *__restrict__ out_len, uint32_t *__restrict__ too_long)
+						    QsRec *__restrict__ rec, uint64_t *__restrict__ out_len, uint32_t *__restrict__ flags, PackCols pk)
 {
 	const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r > n_rec)
 		return;
 	if (r == n_rec) {
 		out_len[r] = 0;
+		if constexpr (PACK) {
+			pk.n_let[r] = pk.n_name[r] = 0;
+			pk.printed[r] = 0;
+		}
 		return;
 	}
 	const Span la = line_of(a, r), lb = line_of(b, r);
@@ -349,12 +473,48 @@ __global__ __launch_bounds__(256) void k_qs_measure(TextView a, TextView b, uint
 	QsRec q = { k1.off, k2.off, (uint32_t)k1.n, (uint32_t)k2.n, fa.hdr_len, fa.pad | dots };
 	uint64_t len = 0;
 	if (la.n >= 0x7FFFFFFFull || lb.n >= 0x7FFFFFFFull) {
-		atomicOr(too_long, 1u);
+		atomicOr(flags, kFlagTooLong);
 	} else if (!zero1 && !zero2) {
 		len = 1 + (uint64_t)fa.hdr_len + fa.pad + 4 + k1.n + gap + k2.n + 1;
 	}
 	rec[r] = q;
 	out_len[r] = len;
+	if constexpr (PACK) {
+		// the header's tabs are printed as ':', so only a blank ends the name; the fields hold no tab and no '\n'
+		uint64_t let = 0, name = 0;
+		uint32_t take = fa.hdr_len;
+		bool blank = false, odd = false;
+		int lead = -1;
+		if (len) {
+			for_bytes(a.text, la.off, (uint64_t)fa.hdr_len, [&](uint8_t c, uint64_t i) {
+				odd |= c == '\r';
+				if (!blank && c == ' ') {
+					blank = true;
+					take = (uint32_t)i;
+				}
+			});
+			name = blank ? take : (uint64_t)fa.hdr_len + fa.pad + 3;
+			auto span = [&](const uint8_t *__restrict__ text, Span s) {
+				for_bytes(text, s.off, s.n, [&](uint8_t c, uint64_t) {
+					odd |= c == '\r';
+					if (lead < 0)
+						lead = c;
+					let += c != ' ' && c != '\t';
+				});
+			};
+			span(a.text, k1);
+			if (lead < 0 && gap)
+				lead = 'N';
+			let += gap;
+			span(b.text, k2);
+			if (odd || lead == '>')
+				atomicOr(flags, kFlagIrregular);
+		}
+		pk.n_let[r] = let;
+		pk.n_name[r] = name;
+		pk.name_take[r] = take | (blank ? 0u : kNameFull);
+		pk.printed[r] = len ? 1u : 0u;
+	}
 }
 
 // the FASTA text of pair `r`, written by one lane group (trim2.4.pl:218-245)
@@ -380,6 +540,41 @@ __global__ __launch_bounds__(256) void k_qs_emit(TextView a, TextView b, uint64_
 	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r < n_rec; r += groups)
 		if (out_off[r + 1] != out_off[r]) // else a mate did not survive: nothing is written for the pair (:199-210)
 			qs_emit_record(a, b, r, gap, rec[r], out_off[r], out);
+}
+
+// The packed route's writer for pairs (k_fq_pack's twin): pair r is record rank[r] of the batch when it prints.
+__global__ __launch_bounds__(256) void k_qs_pack(TextView a, TextView b, uint64_t n_rec, uint64_t gap, const QsRec *__restrict__ rec,
+						 const uint32_t *__restrict__ name_take, const uint32_t *__restrict__ rank,
+						 const uint64_t *__restrict__ let_off, const uint64_t *__restrict__ name_at, char *__restrict__ letters,
+						 char *__restrict__ names, uint32_t *__restrict__ let_off32, uint32_t *__restrict__ name_at32)
+{
+	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
+	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r <= n_rec; r += groups) {
+		const uint32_t k = rank[r];
+		if (r < n_rec && rank[r + 1] == k)
+			continue; // a mate did not survive: the pair is absent
+		uint64_t pos = let_off[r], npos = name_at[r];
+		if ((threadIdx.x & (kGroup - 1)) == 0) {
+			let_off32[k] = (uint32_t)pos;
+			name_at32[k] = (uint32_t)npos;
+		}
+		if (r == n_rec)
+			break;
+		const QsRec q = rec[r];
+		const bool dots = (q.pad_dots & 16u) != 0;
+		const uint32_t take = name_take[r];
+		auto letter = [](uint8_t c) { return c != ' ' && c != '\t'; };
+		auto base = [dots](uint8_t c) { return dots && c == '.' ? (uint8_t)'N' : c; };
+		w_copy(names, npos, a.text + line_of(a, r).off, take & ~kNameFull, [](uint8_t) { return true; },
+		       [](uint8_t c) { return c == '\t' ? (uint8_t)':' : c; });
+		if (take & kNameFull) {
+			w_fill(names, npos, ':', q.pad_dots & 15u);
+			w_lit(names, npos, ":AB", 3);
+		}
+		w_copy(letters, pos, a.text + q.s1, q.n1, letter, base);
+		w_fill(letters, pos, 'N', gap);
+		w_copy(letters, pos, b.text + q.s2, q.n2, letter, base);
+	}
 }
 
 // ------------------------------------------------------------------------------------------------- host side
@@ -475,7 +670,127 @@ static int take_output(const DevBuf<char> &out, uint64_t total, char **text, siz
 	return 0;
 }
 
-static int trim_fastq_device(const std::string &a, bool paired, uint64_t gap, char **text, size_t *len)
+// Where a run's result goes: the FASTA text to the host (pgx_trim_file), or a read batch that stays in HBM (pgx_trim_reads)
+struct TrimSink {
+	char **text = nullptr;
+	size_t *len = nullptr;
+	std::unique_ptr<pgx_reads> *reads = nullptr;
+	int *route = nullptr;
+	bool batch() const { return reads != nullptr; }
+	size_t text_pad() const { return batch() ? 16 : 0; } // the splitter reads aligned 16-byte words
+};
+
+// the FASTA text `out` (in HBM) to the sink: downloaded, or read by the device splitter where it lies (the text route)
+static int deliver_text(DevBuf<char> &out, uint64_t total, const TrimSink &sink)
+{
+	if (!sink.batch()) {
+		const int rc = take_output(out, total, sink.text, sink.len);
+		g_clock.tick("download");
+		return rc;
+	}
+	*sink.route = PGX_TRIM_ROUTE_TEXT;
+	if (total < kDeviceSplitLimit) {
+		PGX_TRY(reads_from_resident_fasta_text((const unsigned char *)out.data(), total, *sink.reads));
+	} else { // texts of 4 GiB and more are split by the host, as in pgx_reads_from_fasta_text
+		char *p = nullptr;
+		size_t n = 0;
+		PGX_TRY(take_output(out, total, &p, &n));
+		out.release();
+		std::string text(p, n);
+		free(p);
+		PGX_TRY(reads_from_fasta_text(std::make_shared<const TextBlob>(std::move(text)), 0, -1, false, nullptr, *sink.reads));
+	}
+	g_clock.tick("text batch");
+	return 0;
+}
+
+// the empty file the script leaves behind (format not recognised, FASTA with -q): no text, or the empty batch
+static int deliver_empty(const TrimSink &sink)
+{
+	if (!sink.batch()) {
+		*sink.text = (char *)calloc(1, 1);
+		return 0;
+	}
+	DevBuf<char> none;
+	PGX_TRY(none.alloc(0, 0, 16));
+	return deliver_text(none, 0, sink);
+}
+
+// The packed route's scans.  `n_let`, `n_name` (and `printed`, QSEQ) hold n_rec + 1 counts; on return `let_off`, `name_at`
+// (and `rank`) hold their exclusive sums, and the totals are on the host.  fits(): both totals are below 2^32, the range of
+// a DeviceFasta's offsets.
+struct PackPlan {
+	DevBuf<uint64_t> n_let, n_name, let_off, name_at;
+	DevBuf<uint32_t> name_take, printed, rank;
+	uint64_t letters = 0, name_bytes = 0, n_out = 0;
+	int alloc(uint64_t n_rec, bool with_rank)
+	{
+		PGX_TRY(n_let.alloc(n_rec + 1));
+		PGX_TRY(n_name.alloc(n_rec + 1));
+		PGX_TRY(name_take.alloc(n_rec + 1));
+		if (with_rank)
+			PGX_TRY(printed.alloc(n_rec + 1));
+		return 0;
+	}
+	PackCols cols() const { return PackCols{ n_let.data(), n_name.data(), name_take.data(), printed.data() }; }
+	int scan(uint64_t n_rec)
+	{
+		PGX_TRY(let_off.alloc(n_rec + 1));
+		PGX_TRY(name_at.alloc(n_rec + 1));
+		PGX_TRY((exclusive_sum<uint64_t, uint64_t>(n_let.data(), let_off.data(), (size_t)n_rec + 1)));
+		PGX_TRY((exclusive_sum<uint64_t, uint64_t>(n_name.data(), name_at.data(), (size_t)n_rec + 1)));
+		PGX_TRY(let_off.download(&letters, 1, n_rec));
+		PGX_TRY(name_at.download(&name_bytes, 1, n_rec));
+		n_out = n_rec;
+		if (printed.base) {
+			uint32_t k = 0;
+			PGX_TRY(rank.alloc(n_rec + 1));
+			PGX_TRY((exclusive_sum<uint32_t, uint32_t>(printed.data(), rank.data(), (size_t)n_rec + 1)));
+			PGX_TRY(rank.download(&k, 1, n_rec));
+			n_out = k;
+		}
+		n_let.release();
+		n_name.release();
+		printed.release();
+		return 0;
+	}
+	bool fits() const { return letters < (1ull << 32) && name_bytes < (1ull << 32); }
+	void release()
+	{
+		n_let.release();
+		n_name.release();
+		let_off.release();
+		name_at.release();
+		name_take.release();
+		printed.release();
+		rank.release();
+	}
+};
+
+// the buffers of a DeviceFasta for `p.n_out` records, for a pack kernel to fill
+static int pack_alloc(const PackPlan &p, DeviceFasta &df, DevBuf<uint32_t> &d_let_off32)
+{
+	PGX_TRY(df.d_letters.alloc(p.letters ? p.letters : 1, 0, 16));
+	PGX_TRY(df.d_names.alloc(p.name_bytes ? p.name_bytes : 1, 0, 16));
+	PGX_TRY(df.d_name_at.alloc(p.n_out + 1));
+	PGX_TRY(d_let_off32.alloc(p.n_out + 1));
+	return 0;
+}
+
+// ... and its host tables, once the kernel has run
+static int pack_tables(const PackPlan &p, DeviceFasta &df, const DevBuf<uint32_t> &d_let_off32)
+{
+	df.let_off.resize(p.n_out + 1);
+	df.name_at.resize(p.n_out + 1);
+	PGX_TRY(d_let_off32.download(df.let_off.data(), p.n_out + 1));
+	PGX_TRY(df.d_name_at.download(df.name_at.data(), p.n_out + 1));
+	df.names.resize(p.name_bytes);
+	if (p.name_bytes)
+		PGX_TRY(df.d_names.download((unsigned char *)&df.names[0], p.name_bytes));
+	return 0;
+}
+
+static int trim_fastq_device(const std::string &a, bool paired, uint64_t gap, const TrimSink &sink)
 {
 	DeviceText da;
 	PGX_TRY(upload_lines(a, da));
@@ -485,24 +800,62 @@ static int trim_fastq_device(const std::string &a, bool paired, uint64_t gap, ch
 	DevBuf<FqRec> rec;
 	DevBuf<uint64_t> out_len;
 	DevBuf<uint32_t> flag;
+	PackPlan plan;
 	PGX_TRY(rec.alloc(n_rec));
 	PGX_TRY(out_len.alloc(n_rec + 1));
 	PGX_TRY(flag.alloc(1, 0, 0, true));
-	hipLaunchKernelGGL(k_fq_measure, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap,
-			   rec.data(), out_len.data(), flag.data());
+	const dim3 grid((unsigned)((n_rec + 1 + 255) / 256));
+	if (sink.batch()) {
+		PGX_TRY(plan.alloc(n_rec, false));
+		hipLaunchKernelGGL(k_fq_measure<true>, grid, dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(), out_len.data(),
+				   flag.data(), plan.cols());
+	} else {
+		hipLaunchKernelGGL(k_fq_measure<false>, grid, dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(), out_len.data(),
+				   flag.data(), PackCols{});
+	}
 	PGX_HIP(hipGetLastError());
+	uint32_t flags = 0;
+	PGX_TRY(flag.download(&flags, 1));
+	if (sink.batch() && !(flags & (kFlagTooLong | kFlagIrregular))) {
+		g_clock.tick("measure");
+		PGX_TRY(plan.scan(n_rec));
+		if (plan.fits()) {
+			out_len.release();
+			DeviceFasta df;
+			DevBuf<uint32_t> d_let_off32;
+			PGX_TRY(pack_alloc(plan, df, d_let_off32));
+			g_clock.tick("scans");
+			hipLaunchKernelGGL(k_fq_pack, dim3(emit_grid(n_rec + 1)), dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(),
+					   plan.name_take.data(), plan.let_off.data(), plan.name_at.data(), (char *)df.d_letters.data(),
+					   (char *)df.d_names.data(), d_let_off32.data(), df.d_name_at.data());
+			PGX_HIP(hipGetLastError());
+			trace_point("trim fastq pack");
+			g_clock.tick("pack");
+			PGX_TRY(pack_tables(plan, df, d_let_off32));
+			// the raw text, its line index and the per-record columns go before the batch is built
+			da.text.release();
+			da.start.release();
+			rec.release();
+			plan.release();
+			d_let_off32.release();
+			g_clock.tick("tables");
+			*sink.route = PGX_TRIM_ROUTE_PACKED;
+			PGX_TRY(reads_from_device_fasta(df, 0, -1, false, nullptr, *sink.reads));
+			g_clock.tick("batch");
+			return 0;
+		}
+	}
+	plan.release();
 	DevBuf<uint64_t> out_off;
 	PGX_TRY(out_off.alloc(n_rec + 1));
 	PGX_TRY((exclusive_sum<uint64_t, uint64_t>(out_len.data(), out_off.data(), (size_t)n_rec + 1)));
 	uint64_t total = 0;
-	uint32_t bad = 0;
 	PGX_TRY(out_off.download(&total, 1, n_rec));
-	PGX_TRY(flag.download(&bad, 1));
 	g_clock.tick("measure");
-	if (bad)
+	if (flags & kFlagTooLong)
 		return fail(PGX_E_LIMIT, "a FASTQ line of 2 GiB or more");
 	DevBuf<char> out;
-	PGX_TRY(out.alloc(total));
+	PGX_TRY(out.alloc(total, 0, sink.text_pad()));
 	if (n_rec) {
 		hipLaunchKernelGGL(k_fq_emit, dim3(emit_grid(n_rec)), dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(),
 				   out_off.data(), out.data());
@@ -510,12 +863,18 @@ static int trim_fastq_device(const std::string &a, bool paired, uint64_t gap, ch
 	}
 	trace_point("trim fastq");
 	g_clock.tick("emit");
-	const int rc = take_output(out, total, text, len);
-	g_clock.tick("download");
-	return rc;
+	if (sink.batch()) {
+		PGX_HIP(hipDeviceSynchronize());
+		da.text.release();
+		da.start.release();
+		rec.release();
+		out_len.release();
+		out_off.release();
+	}
+	return deliver_text(out, total, sink);
 }
 
-static int trim_qseq_device(const std::string &a, const std::string &b, uint64_t gap, long long t1, long long t2, char **text, size_t *len)
+static int trim_qseq_device(const std::string &a, const std::string &b, uint64_t gap, long long t1, long long t2, const TrimSink &sink)
 {
 	DeviceText da, db;
 	PGX_TRY(upload_lines(a, da));
@@ -526,24 +885,63 @@ static int trim_qseq_device(const std::string &a, const std::string &b, uint64_t
 	DevBuf<QsRec> rec;
 	DevBuf<uint64_t> out_len;
 	DevBuf<uint32_t> flag;
+	PackPlan plan;
 	PGX_TRY(rec.alloc(n_rec));
 	PGX_TRY(out_len.alloc(n_rec + 1));
 	PGX_TRY(flag.alloc(1, 0, 0, true));
-	hipLaunchKernelGGL(k_qs_measure, dim3((unsigned)((n_rec + 1 + 255) / 256)), dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, t1, t2,
-			   rec.data(), out_len.data(), flag.data());
+	const dim3 grid((unsigned)((n_rec + 1 + 255) / 256));
+	if (sink.batch()) {
+		PGX_TRY(plan.alloc(n_rec, true));
+		hipLaunchKernelGGL(k_qs_measure<true>, grid, dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, t1, t2, rec.data(), out_len.data(),
+				   flag.data(), plan.cols());
+	} else {
+		hipLaunchKernelGGL(k_qs_measure<false>, grid, dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, t1, t2, rec.data(), out_len.data(),
+				   flag.data(), PackCols{});
+	}
 	PGX_HIP(hipGetLastError());
+	uint32_t flags = 0;
+	PGX_TRY(flag.download(&flags, 1));
+	if (sink.batch() && !(flags & (kFlagTooLong | kFlagIrregular))) {
+		g_clock.tick("measure");
+		PGX_TRY(plan.scan(n_rec));
+		if (plan.fits()) {
+			out_len.release();
+			DeviceFasta df;
+			DevBuf<uint32_t> d_let_off32;
+			PGX_TRY(pack_alloc(plan, df, d_let_off32));
+			g_clock.tick("scans");
+			hipLaunchKernelGGL(k_qs_pack, dim3(emit_grid(n_rec + 1)), dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, rec.data(),
+					   plan.name_take.data(), plan.rank.data(), plan.let_off.data(), plan.name_at.data(),
+					   (char *)df.d_letters.data(), (char *)df.d_names.data(), d_let_off32.data(), df.d_name_at.data());
+			PGX_HIP(hipGetLastError());
+			trace_point("trim qseq pack");
+			g_clock.tick("pack");
+			PGX_TRY(pack_tables(plan, df, d_let_off32));
+			da.text.release();
+			da.start.release();
+			db.text.release();
+			db.start.release();
+			rec.release();
+			plan.release();
+			d_let_off32.release();
+			g_clock.tick("tables");
+			*sink.route = PGX_TRIM_ROUTE_PACKED;
+			PGX_TRY(reads_from_device_fasta(df, 0, -1, false, nullptr, *sink.reads));
+			g_clock.tick("batch");
+			return 0;
+		}
+	}
+	plan.release();
 	DevBuf<uint64_t> out_off;
 	PGX_TRY(out_off.alloc(n_rec + 1));
 	PGX_TRY((exclusive_sum<uint64_t, uint64_t>(out_len.data(), out_off.data(), (size_t)n_rec + 1)));
 	uint64_t total = 0;
-	uint32_t bad = 0;
 	PGX_TRY(out_off.download(&total, 1, n_rec));
-	PGX_TRY(flag.download(&bad, 1));
 	g_clock.tick("measure");
-	if (bad)
+	if (flags & kFlagTooLong)
 		return fail(PGX_E_LIMIT, "a QSEQ line of 2 GiB or more");
 	DevBuf<char> out;
-	PGX_TRY(out.alloc(total));
+	PGX_TRY(out.alloc(total, 0, sink.text_pad()));
 	if (n_rec) {
 		hipLaunchKernelGGL(k_qs_emit, dim3(emit_grid(n_rec)), dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, rec.data(),
 				   out_off.data(), out.data());
@@ -551,9 +949,17 @@ static int trim_qseq_device(const std::string &a, const std::string &b, uint64_t
 	}
 	trace_point("trim qseq");
 	g_clock.tick("emit");
-	const int rc = take_output(out, total, text, len);
-	g_clock.tick("download");
-	return rc;
+	if (sink.batch()) {
+		PGX_HIP(hipDeviceSynchronize());
+		da.text.release();
+		da.start.release();
+		db.text.release();
+		db.start.release();
+		rec.release();
+		out_len.release();
+		out_off.release();
+	}
+	return deliver_text(out, total, sink);
 }
 
 // ------------------------------------------------------------------------------------------------- FASTA input
@@ -875,7 +1281,7 @@ static int parse_fasta_device(const std::string &a, const std::string &q, Text &
 }
 
 // join_fasta (:301-382): the text of the output file
-static int join_fasta_device(const std::string &a, const std::string &b, long long gap, char **text, size_t *len)
+static int join_fasta_device(const std::string &a, const std::string &b, long long gap, const TrimSink &sink)
 {
 	DeviceText da, db;
 	PGX_TRY(upload_lines(a, da));
@@ -901,14 +1307,21 @@ static int join_fasta_device(const std::string &a, const std::string &b, long lo
 	uint64_t total = 0;
 	PGX_TRY(out_off.download(&total, 1, n_iter));
 	DevBuf<char> out;
-	PGX_TRY(out.alloc(total ? total : 1));
+	PGX_TRY(out.alloc(total ? total : 1, 0, sink.text_pad()));
 	if (n_iter) {
 		hipLaunchKernelGGL(k_jf<true>, dim3((unsigned)((n_iter + 127) / 128)), dim3(128), 0, 0, da.view(), db.view(), ta.data(), na, tb.data(), nb,
 				   n_iter, gap, out_len.data(), out_off.data(), out.data());
 		PGX_HIP(hipGetLastError());
 	}
 	trace_point("trim join fasta");
-	return take_output(out, total, text, len);
+	if (!sink.batch())
+		return take_output(out, total, sink.text, sink.len);
+	PGX_HIP(hipDeviceSynchronize());
+	da.text.release();
+	da.start.release();
+	db.text.release();
+	db.start.release();
+	return deliver_text(out, total, sink);
 }
 
 static const char *const kTrimUsage = // trim2.4.pl:54-63
@@ -939,6 +1352,100 @@ static std::string host_field(const std::string &line, int k)
 	}
 }
 
+// the script from its getopts to its closing message; what it writes to RUNBLAST goes to `sink`
+static int trim_run(const pgx_trim_opts *o, Text &log, const TrimSink &sink, int *mode)
+{
+	if (!perl_true(o->a)) { // :53
+		log.s += kTrimUsage;
+		return 0;
+	}
+	bool ok = false;
+	g_clock.tick("start");
+	const std::string a = read_text_file(o->a, &ok);
+	if (!ok) {
+		log.printf("Error: Unable to open %s.\n", o->a); // :68-71
+		return 0;
+	}
+	const bool paired = perl_true(o->b);
+	std::string b;
+	if (paired) {
+		b = read_text_file(o->b, &ok);
+		if (!ok) {
+			log.printf("Error: Unable to open %s.\n", o->b); // :78-81
+			return 0;
+		}
+	}
+	uint64_t gap = 189; // :36
+	long long t1 = 11, t2 = 10; // :35
+	if (perl_true(o->g)) { // :86-88; for ($r = 0; $r < $GAPSIZE; $r++)
+		const double g = perl_num(o->g, strlen(o->g));
+		gap = g > 0 ? (g > 2147483647.0 ? 2147483647ull : (uint64_t)std::ceil(g)) : 0;
+	}
+	if (perl_true(o->t)) { // :90-92
+		const double t = perl_num(o->t, strlen(o->t));
+		if (!(t > -1.0) || !(t < 2147483647.0))
+			return fail(PGX_E_ARG, "-t %s: a negative truncate size is not covered", o->t);
+		t1 = (long long)t;
+		t2 = (long long)(t - 1.0);
+	}
+	g_clock.tick("read files");
+	if (!a.empty() && a[0] == '>') { // :117-143; RUNBLAST was opened before (:115) and stays empty unless -j writes to it
+		if (o->j) {
+			if (paired) {
+				*mode = PGX_TRIM_FASTA_JOIN;
+				long long jg = -1; // `if ($parameters{g})`: without -g no N's at all, $GAPSIZE is not consulted (:338)
+				if (perl_true(o->g)) {
+					const double g = perl_num(o->g, strlen(o->g));
+					jg = g > 0 ? (g > 2147483647.0 ? 2147483647ll : (long long)std::ceil(g)) : 0;
+				}
+				return join_fasta_device(a, b, jg, sink); // exit: no closing message (:124)
+			}
+			log.s += "Error. Input is -j for joining ends, but you did not provided both sequence a and b with -a and -b options.\n\n";
+			*mode = PGX_TRIM_UNKNOWN;
+			return deliver_empty(sink);
+		}
+		*mode = PGX_TRIM_UNKNOWN;
+		PGX_TRY(deliver_empty(sink));
+		if (!perl_true(o->q)) {
+			log.s += "Error: Please, specify the FASTA quality file with -q option.\n";
+			return 0;
+		}
+		log.printf("%s\n", o->q); // :129
+		const std::string q = read_text_file(o->q, &ok);
+		if (!ok) {
+			log.printf("Error: Unable to open %s required for FASTA file triming.\n", o->q);
+			return 0;
+		}
+		*mode = PGX_TRIM_FASTA_QUAL;
+		PGX_TRY(parse_fasta_device(a, q, log));
+		log.s += "Trimming complete.\n";
+		return 0;
+	}
+	if (!a.empty() && a[0] == '@') { // :146-149
+		*mode = PGX_TRIM_FASTQ;
+		PGX_TRY(trim_fastq_device(a, paired, gap, sink));
+	} else {
+		// :152-156: the first line without its first byte
+		std::string first;
+		if (a.size() > 1) {
+			const size_t nl = a.find('\n', 1);
+			first = a.substr(1, (nl == std::string::npos ? a.size() : nl) - 1);
+		}
+		const std::string f7 = host_field(first, 7), f10 = host_field(first, 10);
+		if ((f7 == "1" || f7 == "2") && (f10 == "0" || f10 == "1")) {
+			log.s += "QSEQ file format found.\n";
+			*mode = PGX_TRIM_QSEQ;
+			PGX_TRY(trim_qseq_device(a, b, gap, t1, t2, sink));
+		} else {
+			log.s += "Error: file format not recognized.\n";
+			*mode = PGX_TRIM_UNKNOWN;
+			PGX_TRY(deliver_empty(sink)); // RUNBLAST was opened and stays empty (:115)
+		}
+	}
+	log.s += "Trimming complete.\n"; // :167
+	return 0;
+}
+
 } // namespace pgx
 
 using namespace pgx;
@@ -953,96 +1460,30 @@ extern "C" int pgx_trim_file(const pgx_trim_opts *o, char **log_text, char **fas
 	*mode = PGX_TRIM_NONE;
 	PGX_TRY(require_device());
 	Text log;
-	return with_text(log, log_text, [&]() -> int {
-		if (!perl_true(o->a)) { // :53
-			log.s += kTrimUsage;
-			return 0;
-		}
-		bool ok = false;
-		g_clock.tick("start");
-		const std::string a = read_text_file(o->a, &ok);
-		if (!ok) {
-			log.printf("Error: Unable to open %s.\n", o->a); // :68-71
-			return 0;
-		}
-		const bool paired = perl_true(o->b);
-		std::string b;
-		if (paired) {
-			b = read_text_file(o->b, &ok);
-			if (!ok) {
-				log.printf("Error: Unable to open %s.\n", o->b); // :78-81
-				return 0;
-			}
-		}
-		uint64_t gap = 189; // :36
-		long long t1 = 11, t2 = 10; // :35
-		if (perl_true(o->g)) { // :86-88; for ($r = 0; $r < $GAPSIZE; $r++)
-			const double g = perl_num(o->g, strlen(o->g));
-			gap = g > 0 ? (g > 2147483647.0 ? 2147483647ull : (uint64_t)std::ceil(g)) : 0;
-		}
-		if (perl_true(o->t)) { // :90-92
-			const double t = perl_num(o->t, strlen(o->t));
-			if (!(t > -1.0) || !(t < 2147483647.0))
-				return fail(PGX_E_ARG, "-t %s: a negative truncate size is not covered", o->t);
-			t1 = (long long)t;
-			t2 = (long long)(t - 1.0);
-		}
-		g_clock.tick("read files");
-		if (!a.empty() && a[0] == '>') { // :117-143; RUNBLAST was opened before (:115) and stays empty unless -j writes to it
-			if (o->j) {
-				if (paired) {
-					*mode = PGX_TRIM_FASTA_JOIN;
-					long long jg = -1; // `if ($parameters{g})`: without -g no N's at all, $GAPSIZE is not consulted (:338)
-					if (perl_true(o->g)) {
-						const double g = perl_num(o->g, strlen(o->g));
-						jg = g > 0 ? (g > 2147483647.0 ? 2147483647ll : (long long)std::ceil(g)) : 0;
-					}
-					return join_fasta_device(a, b, jg, fasta_text, fasta_len); // exit: no closing message (:124)
-				}
-				log.s += "Error. Input is -j for joining ends, but you did not provided both sequence a and b with -a and -b options.\n\n";
-				*mode = PGX_TRIM_UNKNOWN;
-				*fasta_text = (char *)calloc(1, 1);
-				return 0;
-			}
-			*mode = PGX_TRIM_UNKNOWN;
-			*fasta_text = (char *)calloc(1, 1);
-			if (!perl_true(o->q)) {
-				log.s += "Error: Please, specify the FASTA quality file with -q option.\n";
-				return 0;
-			}
-			log.printf("%s\n", o->q); // :129
-			const std::string q = read_text_file(o->q, &ok);
-			if (!ok) {
-				log.printf("Error: Unable to open %s required for FASTA file triming.\n", o->q);
-				return 0;
-			}
-			*mode = PGX_TRIM_FASTA_QUAL;
-			PGX_TRY(parse_fasta_device(a, q, log));
-			log.s += "Trimming complete.\n";
-			return 0;
-		}
-		if (!a.empty() && a[0] == '@') { // :146-149
-			*mode = PGX_TRIM_FASTQ;
-			PGX_TRY(trim_fastq_device(a, paired, gap, fasta_text, fasta_len));
-		} else {
-			// :152-156: the first line without its first byte
-			std::string first;
-			if (a.size() > 1) {
-				const size_t nl = a.find('\n', 1);
-				first = a.substr(1, (nl == std::string::npos ? a.size() : nl) - 1);
-			}
-			const std::string f7 = host_field(first, 7), f10 = host_field(first, 10);
-			if ((f7 == "1" || f7 == "2") && (f10 == "0" || f10 == "1")) {
-				log.s += "QSEQ file format found.\n";
-				*mode = PGX_TRIM_QSEQ;
-				PGX_TRY(trim_qseq_device(a, b, gap, t1, t2, fasta_text, fasta_len));
-			} else {
-				log.s += "Error: file format not recognized.\n";
-				*mode = PGX_TRIM_UNKNOWN;
-				*fasta_text = (char *)calloc(1, 1); // RUNBLAST was opened and stays empty (:115)
-			}
-		}
-		log.s += "Trimming complete.\n"; // :167
-		return 0;
-	});
+	TrimSink sink;
+	sink.text = fasta_text;
+	sink.len = fasta_len;
+	return with_text(log, log_text, [&]() -> int { return trim_run(o, log, sink, mode); });
+}
+
+extern "C" int pgx_trim_reads(const pgx_trim_opts *o, char **log_text, pgx_reads **out, int *mode, int *route)
+{
+	if (!o || !log_text || !out || !mode || !route)
+		return fail(PGX_E_ARG, "pgx_trim_reads: null argument");
+	*log_text = nullptr;
+	*out = nullptr;
+	*mode = PGX_TRIM_NONE;
+	*route = PGX_TRIM_ROUTE_NONE;
+	PGX_TRY(require_device());
+	Text log;
+	std::unique_ptr<pgx_reads> rd;
+	TrimSink sink;
+	sink.reads = &rd;
+	sink.route = route;
+	const int rc = with_text(log, log_text, [&]() -> int { return trim_run(o, log, sink, mode); });
+	if (rc == 0)
+		*out = rd.release();
+	else
+		*route = PGX_TRIM_ROUTE_NONE;
+	return rc;
 }

@@ -83,7 +83,16 @@ def main():
         for k, name in enumerate(names):
             print("    %-30s %7.3f s" % (name, t[k + 1] - t[k]))
         print("    %-30s %7.3f s  = %.2f M pairs/s raw reads to table" % ("total", t[-1] - t[0], n / (t[-1] - t[0]) / 1e6), flush=True)
+        # the first two lines as one call: the batch built in HBM, no FASTA text in between (pgx_trim_reads)
+        n_reads = len(reads)
         del hits, reads, rdps
+        t1 = time.time()
+        direct, _messages, _mode, route = pg.Reads.from_trim(os.path.join(d, "a.txt"), b=os.path.join(d, "b.txt"), g=100)
+        dt = time.time() - t1
+        assert len(direct) == n_reads
+        print("    %-30s %7.3f s  (route %s) in place of the first two lines' %.3f s" % ("trim2 -> resident batch", dt,
+              {pg.TRIM_ROUTE_PACKED: "packed", pg.TRIM_ROUTE_TEXT: "text"}[route], t[2] - t[0]), flush=True)
+        del direct
 
 
 if __name__ == "__main__":

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the trim2 drop-in on a synthetic FASTQ / QSEQ file (PGX_TRIM_TIMES=1 prints the stage times), with
-the oracle (C restatement, one core) timed on the same file.  Usage: python3 tools/probe_trim.py [records] [fastq|qseq]"""
+the oracle (C restatement, one core) timed on the same file; then the hand-over to Classify both ways, five runs each: trim2
+and a read batch from its text, against the one call that builds the batch in HBM (Reads.from_trim; its stages are the
+"measure", "scans", "pack", "tables" and "batch" ticks).  Usage: python3 tools/probe_trim.py [records] [fastq|qseq]"""
 import os
 import subprocess
 import sys
@@ -82,6 +84,31 @@ def main():
     dt = time.time() - t0
     want = open(os.path.join(d, "output_files", "trim2", "a.txt_runblast.fasta"), "rb").read()
     print("oracle (1 core): %.3f s -> %.2f M records/s; identical: %s" % (dt, n / dt / 1e6, want == fasta))
+    del want
+
+    def spread(name, times):
+        ts = sorted(times)
+        print("%-34s min %.3f  median %.3f  max %.3f s  (%d runs)" % (name, ts[0], ts[len(ts) // 2], ts[-1], len(ts)), flush=True)
+    two, one = [], []
+    for rep in range(5):
+        print("-- two calls, run %d" % rep, file=sys.stderr, flush=True)
+        t0 = time.time()
+        out, fasta, mode = pg.trim2(a, **args)
+        t1 = time.time()
+        reads = pg.Reads.from_fasta_text(fasta)
+        two.append((t1 - t0, time.time() - t1))
+        n_reads = len(reads)
+        del reads, fasta
+        print("-- one call, run %d" % rep, file=sys.stderr, flush=True)
+        t0 = time.time()
+        reads, _out, _mode, route = pg.Reads.from_trim(a, **args)
+        one.append(time.time() - t0)
+        assert len(reads) == n_reads
+        del reads
+    spread("trim2 (files -> FASTA text)", [x for x, _ in two])
+    spread("read batch from that text", [y for _, y in two])
+    spread("the two together", [x + y for x, y in two])
+    spread("trim2 -> resident batch (%s)" % {pg.TRIM_ROUTE_PACKED: "packed", pg.TRIM_ROUTE_TEXT: "text"}[route], one)
 
 
 if __name__ == "__main__":
