@@ -5,9 +5,10 @@
 //   k_nl_count / k_nl_write   line index of the text (one start offset per line), 16 KB tiles, two passes
 //   k_fq_measure / k_qs_measure   one lane per output record: the script's running-sum quality rule
 //                                 (trim2.4.pl:543-563, :272-287), the kept span of each mate, the record's output size
-//   k_fq_emit / k_qs_emit     16 lanes per record write its FASTA text (header rewrite, white-space removal,
-//                             '.' -> N, the $GAPSIZE N's between mates) at the offset an exclusive scan gave it
-// The host keeps what the script does before it reads a record: getopts, the open checks, format detection on
+//   k_fq_write / k_qs_write   16 lanes per record write it (header rewrite, white-space removal, '.' -> N, the $GAPSIZE
+//                             N's between mates) at the offset an exclusive scan gave it.  A format's record is stated
+//                             once (fq_record, qs_record) over a sink: TextOut = its FASTA text, PackOut = see below
+// The host sequence is one function for both formats (trim_records_device over a Fastq or a Qseq).  The host keeps what the script does before it reads a record: getopts, the open checks, format detection on
 // the first line, and the messages.  What the script's Perl actually computes (several statements have no
 // effect) is written out in oracle/o_trim.c's header, which the parity tests pin on the reference's own output.
 //
@@ -18,7 +19,7 @@
 //
 // pgx_trim_reads (the end of this file) is the same run handed to Classify without the FASTA text: the measure kernels also
 // count each record's letters and name bytes as the FASTA splitter (seqdb.hip) would find them, two more scans give the
-// offsets, and k_fq_pack / k_qs_pack write the compact letters and the names straight from the raw lines (the packed route).
+// offsets, and the writers' PackOut form puts the compact letters and the names there straight from the raw lines (the packed route).
 // A call with a record whose text the splitter would read differently (below: "regular") writes the FASTA into HBM as
 // before and lets the splitter read it there (the text route).
 #include <rocprim/device/device_scan.hpp>
@@ -294,77 +295,117 @@ __global__ __launch_bounds__(256) void k_fq_measure(TextView t, uint64_t n_rec, 
 	}
 }
 
-// the FASTA text of record `r`, written by one lane group (trim2.4.pl:487-515)
-__device__ void fq_emit_record(const TextView &t, uint64_t r, int paired, uint64_t gap, const FqRec f, uint64_t pos, char *__restrict__ out)
+// ------------------------------------------------------------------------------------------------- record writers
+// A format states its record once (fq_record, qs_record) over a sink, which says where the bytes go.  One lane group writes
+// a record; its lanes call a sink's members together.  The text sink is the FASTA text the script prints.  The pack sink
+// is that text as the FASTA splitter would read it back: the header's first word to one cursor, the letters (no blank, no
+// tab) to another, nothing for '>', the tab and the line ends.  Either is also what its kernel is handed by the host: the
+// pointers are the host's, the cursors (and `take`) are set per record.
+struct TextOut {
+	static constexpr bool kPack = false;
+	const uint64_t *out_off; // exclusive scan of the records' sizes
+	char *out;
+	uint64_t pos;
+	__device__ __forceinline__ void seek(uint64_t r) { pos = out_off[r]; }
+	// '>', the `n` header bytes, one ':' per field a short QSEQ line lacks, the script's suffix
+	template <typename Keep, typename Map>
+	__device__ __forceinline__ void header(const uint8_t *src, uint64_t n, uint32_t pad, const Keep &keep, const Map &map)
+	{
+		w_lit(out, pos, ">", 1);
+		w_copy(out, pos, src, n, keep, map);
+		w_fill(out, pos, ':', pad);
+		w_lit(out, pos, ":AB\n", 4);
+	}
+	template <typename Keep, typename Map> __device__ __forceinline__ void bases(const uint8_t *src, uint64_t n, const Keep &keep, const Map &map)
+	{
+		w_copy(out, pos, src, n, keep, map);
+	}
+	__device__ __forceinline__ void run(char c, uint64_t n) { w_fill(out, pos, c, n); }
+	__device__ __forceinline__ void zero() { w_lit(out, pos, "0", 1); } // the mate that became the number 0
+	__device__ __forceinline__ void mark(const char *c) { w_lit(out, pos, c, 1); } // a tab or a line end
+};
+
+struct PackOut {
+	static constexpr bool kPack = true;
+	const uint32_t *name_take, *rank;    // PackCols::name_take; rank: QSEQ only
+	const uint64_t *let_off, *name_at;   // per input record (+ the totals): where its letters and its name begin
+	char *letters, *names;
+	uint32_t *let_off32, *name_at32;     // per batch record (+ the totals): the same as the 32-bit entries of a DeviceFasta
+	uint64_t pos, npos;
+	uint32_t take;
+	// input record `r` is record `k` of the batch; r = n_rec gives the closing offsets
+	__device__ __forceinline__ void seek(uint64_t r, uint64_t k)
+	{
+		pos = let_off[r];
+		npos = name_at[r];
+		if ((threadIdx.x & (kGroup - 1)) == 0) {
+			let_off32[k] = (uint32_t)pos;
+			name_at32[k] = (uint32_t)npos;
+		}
+	}
+	// the name: the header cut at its first blank (`n`, the whole header, is not looked at), or all of it through the suffix
+	template <typename Keep, typename Map>
+	__device__ __forceinline__ void header(const uint8_t *src, uint64_t, uint32_t pad, const Keep &keep, const Map &map)
+	{
+		w_copy(names, npos, src, take & ~kNameFull, keep, map);
+		if (take & kNameFull) {
+			w_fill(names, npos, ':', pad);
+			w_lit(names, npos, ":AB", 3);
+		}
+	}
+	template <typename Keep, typename Map> __device__ __forceinline__ void bases(const uint8_t *src, uint64_t n, const Keep &keep, const Map &map)
+	{
+		w_copy(letters, pos, src, n, [keep](uint8_t c) { return keep(c) && c != ' ' && c != '\t'; }, map);
+	}
+	__device__ __forceinline__ void run(char c, uint64_t n) { w_fill(letters, pos, c, n); }
+	__device__ __forceinline__ void zero() { w_lit(letters, pos, "0", 1); }
+	__device__ __forceinline__ void mark(const char *) {}
+};
+
+// the lane groups of a bounded grid (emit_grid) stride over the records
+__device__ __forceinline__ uint64_t first_record() { return (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; }
+__device__ __forceinline__ uint64_t record_stride() { return (uint64_t)gridDim.x * (blockDim.x / kGroup); }
+
+// record `r` (trim2.4.pl:487-515)
+template <typename Out>
+__device__ void fq_record(const TextView &t, uint64_t r, int paired, uint64_t gap, const FqRec f, Out &s)
 {
 	const uint64_t l0 = r * (paired ? 8 : 4);
 	Span hdr = line_of(t, l0);
 	if (hdr.n && t.text[hdr.off + hdr.n - 1] == '\n')
 		hdr.n--;
 	auto same = [](uint8_t c) { return c; };
-	w_lit(out, pos, ">", 1);
-	w_copy(out, pos, t.text + hdr.off, hdr.n, [](uint8_t c) { return c != '@'; }, same);
-	w_lit(out, pos, ":AB\n", 4);
+	s.header(t.text + hdr.off, hdr.n, 0, [](uint8_t c) { return c != '@'; }, same);
 	if (f.keep1 != kZeroRead)
-		w_copy(out, pos, t.text + line_of(t, l0 + 1).off, f.keep1, [](uint8_t c) { return !p_space_dev(c); }, same);
+		s.bases(t.text + line_of(t, l0 + 1).off, f.keep1, [](uint8_t c) { return !p_space_dev(c); }, same);
 	else
-		w_lit(out, pos, "0", 1);
+		s.zero();
 	if (paired) {
-		w_fill(out, pos, 'N', gap);
+		s.run('N', gap);
 		if (f.keep2 != kZeroRead) {
-			w_copy(out, pos, t.text + line_of(t, l0 + 5).off, f.keep2, [](uint8_t) { return true; }, same);
-			w_lit(out, pos, "\t", 1);
+			s.bases(t.text + line_of(t, l0 + 5).off, f.keep2, [](uint8_t) { return true; }, same);
+			s.mark("\t"); // the second mate keeps its tab (:571, :508)
 		} else {
-			w_lit(out, pos, "0", 1);
+			s.zero();
 		}
 	}
-	w_lit(out, pos, "\n", 1);
+	s.mark("\n");
 }
 
-// a bounded grid of lane groups strides over the records
-__global__ __launch_bounds__(256) void k_fq_emit(TextView t, uint64_t n_rec, int paired, uint64_t gap, const FqRec *__restrict__ rec,
-						 const uint64_t *__restrict__ out_off, char *__restrict__ out)
+// PackOut: one group more than records, for the closing offsets
+template <typename Out>
+__global__ __launch_bounds__(256) void k_fq_write(TextView t, uint64_t n_rec, int paired, uint64_t gap, const FqRec *__restrict__ rec, Out s)
 {
-	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
-	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r < n_rec; r += groups)
-		fq_emit_record(t, r, paired, gap, rec[r], out_off[r], out);
-}
-
-// The packed route's writer: what fq_emit_record prints, as the splitter would read it back -- the letters of record r (no
-// blanks, no tabs) at let_off[r], the first word of its header at name_at[r] -- and the two offsets as the 32-bit entries
-// of a DeviceFasta.  One lane group per record; group n_rec writes the closing offsets.
-__global__ __launch_bounds__(256) void k_fq_pack(TextView t, uint64_t n_rec, int paired, uint64_t gap, const FqRec *__restrict__ rec,
-						 const uint32_t *__restrict__ name_take, const uint64_t *__restrict__ let_off,
-						 const uint64_t *__restrict__ name_at, char *__restrict__ letters, char *__restrict__ names,
-						 uint32_t *__restrict__ let_off32, uint32_t *__restrict__ name_at32)
-{
-	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
-	auto same = [](uint8_t c) { return c; };
-	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r <= n_rec; r += groups) {
-		uint64_t pos = let_off[r], npos = name_at[r];
-		if ((threadIdx.x & (kGroup - 1)) == 0) {
-			let_off32[r] = (uint32_t)pos;
-			name_at32[r] = (uint32_t)npos;
+	for (uint64_t r = first_record(); r < n_rec + Out::kPack; r += record_stride()) {
+		if constexpr (Out::kPack) {
+			s.seek(r, r);
+			if (r == n_rec)
+				break;
+			s.take = s.name_take[r];
+		} else {
+			s.seek(r);
 		}
-		if (r == n_rec)
-			break;
-		const uint64_t l0 = r * (paired ? 8 : 4);
-		const FqRec f = rec[r];
-		const uint32_t take = name_take[r];
-		w_copy(names, npos, t.text + line_of(t, l0).off, take & ~kNameFull, [](uint8_t c) { return c != '@'; }, same);
-		if (take & kNameFull)
-			w_lit(names, npos, ":AB", 3);
-		if (f.keep1 != kZeroRead)
-			w_copy(letters, pos, t.text + line_of(t, l0 + 1).off, f.keep1, [](uint8_t c) { return !p_space_dev(c); }, same);
-		else
-			w_lit(letters, pos, "0", 1);
-		if (paired) {
-			w_fill(letters, pos, 'N', gap);
-			if (f.keep2 != kZeroRead)
-				w_copy(letters, pos, t.text + line_of(t, l0 + 5).off, f.keep2, [](uint8_t c) { return c != ' ' && c != '\t'; }, same);
-			else
-				w_lit(letters, pos, "0", 1);
-		}
+		fq_record(t, r, paired, gap, rec[r], s);
 	}
 }
 
@@ -517,63 +558,39 @@ __global__ __launch_bounds__(256) void k_qs_measure(TextView a, TextView b, uint
 	}
 }
 
-// the FASTA text of pair `r`, written by one lane group (trim2.4.pl:218-245)
-__device__ void qs_emit_record(const TextView &a, const TextView &b, uint64_t r, uint64_t gap, const QsRec q, uint64_t pos, char *__restrict__ out)
+// pair `r` (trim2.4.pl:218-245)
+template <typename Out>
+__device__ void qs_record(const TextView &a, const TextView &b, uint64_t r, uint64_t gap, const QsRec q, Out &s)
 {
 	const bool dots = (q.pad_dots & 16u) != 0;
 	auto all = [](uint8_t) { return true; };
 	auto base = [dots](uint8_t c) { return dots && c == '.' ? (uint8_t)'N' : c; };
-	w_lit(out, pos, ">", 1);
-	w_copy(out, pos, a.text + line_of(a, r).off, q.hdr_len, all, [](uint8_t c) { return c == '\t' ? (uint8_t)':' : c; });
-	w_fill(out, pos, ':', q.pad_dots & 15u);
-	w_lit(out, pos, ":AB\n", 4);
-	w_copy(out, pos, a.text + q.s1, q.n1, all, base);
-	w_fill(out, pos, 'N', gap);
-	w_copy(out, pos, b.text + q.s2, q.n2, all, base);
-	w_lit(out, pos, "\n", 1);
+	s.header(a.text + line_of(a, r).off, q.hdr_len, q.pad_dots & 15u, all, [](uint8_t c) { return c == '\t' ? (uint8_t)':' : c; });
+	s.bases(a.text + q.s1, q.n1, all, base);
+	s.run('N', gap);
+	s.bases(b.text + q.s2, q.n2, all, base);
+	s.mark("\n");
 }
 
-__global__ __launch_bounds__(256) void k_qs_emit(TextView a, TextView b, uint64_t n_rec, uint64_t gap, const QsRec *__restrict__ rec,
-						 const uint64_t *__restrict__ out_off, char *__restrict__ out)
+// A pair one of whose mates did not survive is absent (:199-210): its size is 0; PackOut: it has the rank of the next pair
+template <typename Out>
+__global__ __launch_bounds__(256) void k_qs_write(TextView a, TextView b, uint64_t n_rec, uint64_t gap, const QsRec *__restrict__ rec, Out s)
 {
-	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
-	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r < n_rec; r += groups)
-		if (out_off[r + 1] != out_off[r]) // else a mate did not survive: nothing is written for the pair (:199-210)
-			qs_emit_record(a, b, r, gap, rec[r], out_off[r], out);
-}
-
-// The packed route's writer for pairs (k_fq_pack's twin): pair r is record rank[r] of the batch when it prints.
-__global__ __launch_bounds__(256) void k_qs_pack(TextView a, TextView b, uint64_t n_rec, uint64_t gap, const QsRec *__restrict__ rec,
-						 const uint32_t *__restrict__ name_take, const uint32_t *__restrict__ rank,
-						 const uint64_t *__restrict__ let_off, const uint64_t *__restrict__ name_at, char *__restrict__ letters,
-						 char *__restrict__ names, uint32_t *__restrict__ let_off32, uint32_t *__restrict__ name_at32)
-{
-	const uint64_t groups = (uint64_t)gridDim.x * (blockDim.x / kGroup);
-	for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x / kGroup) + threadIdx.x / kGroup; r <= n_rec; r += groups) {
-		const uint32_t k = rank[r];
-		if (r < n_rec && rank[r + 1] == k)
-			continue; // a mate did not survive: the pair is absent
-		uint64_t pos = let_off[r], npos = name_at[r];
-		if ((threadIdx.x & (kGroup - 1)) == 0) {
-			let_off32[k] = (uint32_t)pos;
-			name_at32[k] = (uint32_t)npos;
+	for (uint64_t r = first_record(); r < n_rec + Out::kPack; r += record_stride()) {
+		if constexpr (Out::kPack) {
+			const uint32_t k = s.rank[r];
+			if (r < n_rec && s.rank[r + 1] == k)
+				continue;
+			s.seek(r, k);
+			if (r == n_rec)
+				break;
+			s.take = s.name_take[r];
+		} else {
+			if (s.out_off[r + 1] == s.out_off[r])
+				continue;
+			s.seek(r);
 		}
-		if (r == n_rec)
-			break;
-		const QsRec q = rec[r];
-		const bool dots = (q.pad_dots & 16u) != 0;
-		const uint32_t take = name_take[r];
-		auto letter = [](uint8_t c) { return c != ' ' && c != '\t'; };
-		auto base = [dots](uint8_t c) { return dots && c == '.' ? (uint8_t)'N' : c; };
-		w_copy(names, npos, a.text + line_of(a, r).off, take & ~kNameFull, [](uint8_t) { return true; },
-		       [](uint8_t c) { return c == '\t' ? (uint8_t)':' : c; });
-		if (take & kNameFull) {
-			w_fill(names, npos, ':', q.pad_dots & 15u);
-			w_lit(names, npos, ":AB", 3);
-		}
-		w_copy(letters, pos, a.text + q.s1, q.n1, letter, base);
-		w_fill(letters, pos, 'N', gap);
-		w_copy(letters, pos, b.text + q.s2, q.n2, letter, base);
+		qs_record(a, b, r, gap, rec[r], s);
 	}
 }
 
@@ -583,6 +600,11 @@ struct DeviceText {
 	DevBuf<uint64_t> start;
 	uint64_t n = 0, n_lines = 0;
 	TextView view() const { return TextView{ text.data(), start.data(), n_lines }; }
+	void release()
+	{
+		text.release();
+		start.release();
+	}
 };
 
 template <typename In, typename Out> static int exclusive_sum(const In *in, Out *out, size_t n)
@@ -790,140 +812,105 @@ static int pack_tables(const PackPlan &p, DeviceFasta &df, const DevBuf<uint32_t
 	return 0;
 }
 
-static int trim_fastq_device(const std::string &a, bool paired, uint64_t gap, const TrimSink &sink)
-{
-	DeviceText da;
-	PGX_TRY(upload_lines(a, da));
-	const uint64_t per = paired ? 8 : 4, n_rec = (da.n_lines + per - 1) / per;
-	if (n_rec >= 0x7FFFFFFFull)
-		return fail(PGX_E_LIMIT, "%llu FASTQ records in one call", (unsigned long long)n_rec);
-	DevBuf<FqRec> rec;
-	DevBuf<uint64_t> out_len;
-	DevBuf<uint32_t> flag;
-	PackPlan plan;
-	PGX_TRY(rec.alloc(n_rec));
-	PGX_TRY(out_len.alloc(n_rec + 1));
-	PGX_TRY(flag.alloc(1, 0, 0, true));
-	const dim3 grid((unsigned)((n_rec + 1 + 255) / 256));
-	if (sink.batch()) {
-		PGX_TRY(plan.alloc(n_rec, false));
-		hipLaunchKernelGGL(k_fq_measure<true>, grid, dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(), out_len.data(),
-				   flag.data(), plan.cols());
-	} else {
-		hipLaunchKernelGGL(k_fq_measure<false>, grid, dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(), out_len.data(),
-				   flag.data(), PackCols{});
+// What differs between the two formats in trim_records_device: the input texts, the record count and type, whether a record
+// can be absent (the rank column of the packed route), the kernels, and the format's words in the limit messages.
+struct Fastq {
+	using Rec = FqRec;
+	static constexpr bool kRank = false;
+	static constexpr const char *kName = "FASTQ", *kCounted = "FASTQ records", *kTrace = "trim fastq", *kTracePack = "trim fastq pack";
+	DeviceText a;
+	bool paired = false;
+	uint64_t gap = 0;
+	uint64_t n_rec() const { return (a.n_lines + (paired ? 8 : 4) - 1) / (paired ? 8 : 4); }
+	template <bool PACK> void measure(dim3 grid, FqRec *rec, uint64_t *out_len, uint32_t *flags, PackCols pk) const
+	{
+		hipLaunchKernelGGL(k_fq_measure<PACK>, grid, dim3(256), 0, 0, a.view(), n_rec(), paired ? 1 : 0, gap, rec, out_len, flags, pk);
 	}
-	PGX_HIP(hipGetLastError());
-	uint32_t flags = 0;
-	PGX_TRY(flag.download(&flags, 1));
-	if (sink.batch() && !(flags & (kFlagTooLong | kFlagIrregular))) {
-		g_clock.tick("measure");
-		PGX_TRY(plan.scan(n_rec));
-		if (plan.fits()) {
-			out_len.release();
-			DeviceFasta df;
-			DevBuf<uint32_t> d_let_off32;
-			PGX_TRY(pack_alloc(plan, df, d_let_off32));
-			g_clock.tick("scans");
-			hipLaunchKernelGGL(k_fq_pack, dim3(emit_grid(n_rec + 1)), dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(),
-					   plan.name_take.data(), plan.let_off.data(), plan.name_at.data(), (char *)df.d_letters.data(),
-					   (char *)df.d_names.data(), d_let_off32.data(), df.d_name_at.data());
-			PGX_HIP(hipGetLastError());
-			trace_point("trim fastq pack");
-			g_clock.tick("pack");
-			PGX_TRY(pack_tables(plan, df, d_let_off32));
-			// the raw text, its line index and the per-record columns go before the batch is built
-			da.text.release();
-			da.start.release();
-			rec.release();
-			plan.release();
-			d_let_off32.release();
-			g_clock.tick("tables");
-			*sink.route = PGX_TRIM_ROUTE_PACKED;
-			PGX_TRY(reads_from_device_fasta(df, 0, -1, false, nullptr, *sink.reads));
-			g_clock.tick("batch");
-			return 0;
-		}
+	template <typename Out> void write(dim3 grid, const FqRec *rec, Out out) const
+	{
+		hipLaunchKernelGGL(k_fq_write<Out>, grid, dim3(256), 0, 0, a.view(), n_rec(), paired ? 1 : 0, gap, rec, out);
 	}
-	plan.release();
-	DevBuf<uint64_t> out_off;
-	PGX_TRY(out_off.alloc(n_rec + 1));
-	PGX_TRY((exclusive_sum<uint64_t, uint64_t>(out_len.data(), out_off.data(), (size_t)n_rec + 1)));
-	uint64_t total = 0;
-	PGX_TRY(out_off.download(&total, 1, n_rec));
-	g_clock.tick("measure");
-	if (flags & kFlagTooLong)
-		return fail(PGX_E_LIMIT, "a FASTQ line of 2 GiB or more");
-	DevBuf<char> out;
-	PGX_TRY(out.alloc(total, 0, sink.text_pad()));
-	if (n_rec) {
-		hipLaunchKernelGGL(k_fq_emit, dim3(emit_grid(n_rec)), dim3(256), 0, 0, da.view(), n_rec, paired ? 1 : 0, gap, rec.data(),
-				   out_off.data(), out.data());
-		PGX_HIP(hipGetLastError());
-	}
-	trace_point("trim fastq");
-	g_clock.tick("emit");
-	if (sink.batch()) {
-		PGX_HIP(hipDeviceSynchronize());
-		da.text.release();
-		da.start.release();
-		rec.release();
-		out_len.release();
-		out_off.release();
-	}
-	return deliver_text(out, total, sink);
-}
+	void release() { a.release(); }
+};
 
-static int trim_qseq_device(const std::string &a, const std::string &b, uint64_t gap, long long t1, long long t2, const TrimSink &sink)
-{
-	DeviceText da, db;
-	PGX_TRY(upload_lines(a, da));
-	PGX_TRY(upload_lines(b, db));
-	const uint64_t n_rec = da.n_lines;
-	if (n_rec >= 0x7FFFFFFFull)
-		return fail(PGX_E_LIMIT, "%llu QSEQ lines in one call", (unsigned long long)n_rec);
-	DevBuf<QsRec> rec;
-	DevBuf<uint64_t> out_len;
-	DevBuf<uint32_t> flag;
+struct Qseq {
+	using Rec = QsRec;
+	static constexpr bool kRank = true;
+	static constexpr const char *kName = "QSEQ", *kCounted = "QSEQ lines", *kTrace = "trim qseq", *kTracePack = "trim qseq pack";
+	DeviceText a, b;
+	uint64_t gap = 0;
+	long long t1 = 0, t2 = 0;
+	uint64_t n_rec() const { return a.n_lines; }
+	template <bool PACK> void measure(dim3 grid, QsRec *rec, uint64_t *out_len, uint32_t *flags, PackCols pk) const
+	{
+		hipLaunchKernelGGL(k_qs_measure<PACK>, grid, dim3(256), 0, 0, a.view(), b.view(), n_rec(), gap, t1, t2, rec, out_len, flags, pk);
+	}
+	template <typename Out> void write(dim3 grid, const QsRec *rec, Out out) const
+	{
+		hipLaunchKernelGGL(k_qs_write<Out>, grid, dim3(256), 0, 0, a.view(), b.view(), n_rec(), gap, rec, out);
+	}
+	void release()
+	{
+		a.release();
+		b.release();
+	}
+};
+
+// the per-record columns of one call
+template <typename Rec> struct RecordCols {
+	DevBuf<Rec> rec;
+	DevBuf<uint64_t> out_len, out_off;
+	DevBuf<uint32_t> flag, let_off32;
 	PackPlan plan;
-	PGX_TRY(rec.alloc(n_rec));
-	PGX_TRY(out_len.alloc(n_rec + 1));
-	PGX_TRY(flag.alloc(1, 0, 0, true));
+	void release()
+	{
+		rec.release();
+		out_len.release();
+		out_off.release();
+		flag.release();
+		let_off32.release();
+		plan.release();
+	}
+};
+
+// The uploaded read files `f` to the sink: measure, then the packed route (a batch is wanted and every record is regular) or
+// the text route.  Before a batch is built, everything it is not made of is let go.
+template <typename F> static int trim_records_device(F &f, const TrimSink &sink)
+{
+	const uint64_t n_rec = f.n_rec();
+	if (n_rec >= 0x7FFFFFFFull)
+		return fail(PGX_E_LIMIT, "%llu %s in one call", (unsigned long long)n_rec, F::kCounted);
+	RecordCols<typename F::Rec> c;
+	PGX_TRY(c.rec.alloc(n_rec));
+	PGX_TRY(c.out_len.alloc(n_rec + 1));
+	PGX_TRY(c.flag.alloc(1, 0, 0, true));
 	const dim3 grid((unsigned)((n_rec + 1 + 255) / 256));
 	if (sink.batch()) {
-		PGX_TRY(plan.alloc(n_rec, true));
-		hipLaunchKernelGGL(k_qs_measure<true>, grid, dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, t1, t2, rec.data(), out_len.data(),
-				   flag.data(), plan.cols());
+		PGX_TRY(c.plan.alloc(n_rec, F::kRank));
+		f.template measure<true>(grid, c.rec.data(), c.out_len.data(), c.flag.data(), c.plan.cols());
 	} else {
-		hipLaunchKernelGGL(k_qs_measure<false>, grid, dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, t1, t2, rec.data(), out_len.data(),
-				   flag.data(), PackCols{});
+		f.template measure<false>(grid, c.rec.data(), c.out_len.data(), c.flag.data(), PackCols{});
 	}
 	PGX_HIP(hipGetLastError());
 	uint32_t flags = 0;
-	PGX_TRY(flag.download(&flags, 1));
+	PGX_TRY(c.flag.download(&flags, 1));
 	if (sink.batch() && !(flags & (kFlagTooLong | kFlagIrregular))) {
 		g_clock.tick("measure");
-		PGX_TRY(plan.scan(n_rec));
-		if (plan.fits()) {
-			out_len.release();
+		PGX_TRY(c.plan.scan(n_rec));
+		if (c.plan.fits()) {
+			c.out_len.release();
 			DeviceFasta df;
-			DevBuf<uint32_t> d_let_off32;
-			PGX_TRY(pack_alloc(plan, df, d_let_off32));
+			PGX_TRY(pack_alloc(c.plan, df, c.let_off32));
 			g_clock.tick("scans");
-			hipLaunchKernelGGL(k_qs_pack, dim3(emit_grid(n_rec + 1)), dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, rec.data(),
-					   plan.name_take.data(), plan.rank.data(), plan.let_off.data(), plan.name_at.data(),
-					   (char *)df.d_letters.data(), (char *)df.d_names.data(), d_let_off32.data(), df.d_name_at.data());
+			f.write(dim3(emit_grid(n_rec + 1)), c.rec.data(),
+				PackOut{ c.plan.name_take.data(), c.plan.rank.data(), c.plan.let_off.data(), c.plan.name_at.data(), (char *)df.d_letters.data(),
+					 (char *)df.d_names.data(), c.let_off32.data(), df.d_name_at.data() });
 			PGX_HIP(hipGetLastError());
-			trace_point("trim qseq pack");
+			trace_point(F::kTracePack);
 			g_clock.tick("pack");
-			PGX_TRY(pack_tables(plan, df, d_let_off32));
-			da.text.release();
-			da.start.release();
-			db.text.release();
-			db.start.release();
-			rec.release();
-			plan.release();
-			d_let_off32.release();
+			PGX_TRY(pack_tables(c.plan, df, c.let_off32));
+			f.release();
+			c.release();
 			g_clock.tick("tables");
 			*sink.route = PGX_TRIM_ROUTE_PACKED;
 			PGX_TRY(reads_from_device_fasta(df, 0, -1, false, nullptr, *sink.reads));
@@ -931,33 +918,26 @@ static int trim_qseq_device(const std::string &a, const std::string &b, uint64_t
 			return 0;
 		}
 	}
-	plan.release();
-	DevBuf<uint64_t> out_off;
-	PGX_TRY(out_off.alloc(n_rec + 1));
-	PGX_TRY((exclusive_sum<uint64_t, uint64_t>(out_len.data(), out_off.data(), (size_t)n_rec + 1)));
+	c.plan.release();
+	PGX_TRY(c.out_off.alloc(n_rec + 1));
+	PGX_TRY((exclusive_sum<uint64_t, uint64_t>(c.out_len.data(), c.out_off.data(), (size_t)n_rec + 1)));
 	uint64_t total = 0;
-	PGX_TRY(out_off.download(&total, 1, n_rec));
+	PGX_TRY(c.out_off.download(&total, 1, n_rec));
 	g_clock.tick("measure");
 	if (flags & kFlagTooLong)
-		return fail(PGX_E_LIMIT, "a QSEQ line of 2 GiB or more");
+		return fail(PGX_E_LIMIT, "a %s line of 2 GiB or more", F::kName);
 	DevBuf<char> out;
 	PGX_TRY(out.alloc(total, 0, sink.text_pad()));
 	if (n_rec) {
-		hipLaunchKernelGGL(k_qs_emit, dim3(emit_grid(n_rec)), dim3(256), 0, 0, da.view(), db.view(), n_rec, gap, rec.data(),
-				   out_off.data(), out.data());
+		f.write(dim3(emit_grid(n_rec)), c.rec.data(), TextOut{ c.out_off.data(), out.data() });
 		PGX_HIP(hipGetLastError());
 	}
-	trace_point("trim qseq");
+	trace_point(F::kTrace);
 	g_clock.tick("emit");
 	if (sink.batch()) {
 		PGX_HIP(hipDeviceSynchronize());
-		da.text.release();
-		da.start.release();
-		db.text.release();
-		db.start.release();
-		rec.release();
-		out_len.release();
-		out_off.release();
+		f.release();
+		c.release();
 	}
 	return deliver_text(out, total, sink);
 }
@@ -1314,13 +1294,11 @@ static int join_fasta_device(const std::string &a, const std::string &b, long lo
 		PGX_HIP(hipGetLastError());
 	}
 	trace_point("trim join fasta");
-	if (!sink.batch())
-		return take_output(out, total, sink.text, sink.len);
-	PGX_HIP(hipDeviceSynchronize());
-	da.text.release();
-	da.start.release();
-	db.text.release();
-	db.start.release();
+	if (sink.batch()) {
+		PGX_HIP(hipDeviceSynchronize());
+		da.release();
+		db.release();
+	}
 	return deliver_text(out, total, sink);
 }
 
@@ -1423,7 +1401,11 @@ static int trim_run(const pgx_trim_opts *o, Text &log, const TrimSink &sink, int
 	}
 	if (!a.empty() && a[0] == '@') { // :146-149
 		*mode = PGX_TRIM_FASTQ;
-		PGX_TRY(trim_fastq_device(a, paired, gap, sink));
+		Fastq f;
+		f.paired = paired;
+		f.gap = gap;
+		PGX_TRY(upload_lines(a, f.a));
+		PGX_TRY(trim_records_device(f, sink));
 	} else {
 		// :152-156: the first line without its first byte
 		std::string first;
@@ -1435,7 +1417,13 @@ static int trim_run(const pgx_trim_opts *o, Text &log, const TrimSink &sink, int
 		if ((f7 == "1" || f7 == "2") && (f10 == "0" || f10 == "1")) {
 			log.s += "QSEQ file format found.\n";
 			*mode = PGX_TRIM_QSEQ;
-			PGX_TRY(trim_qseq_device(a, b, gap, t1, t2, sink));
+			Qseq f;
+			f.gap = gap;
+			f.t1 = t1;
+			f.t2 = t2;
+			PGX_TRY(upload_lines(a, f.a));
+			PGX_TRY(upload_lines(b, f.b));
+			PGX_TRY(trim_records_device(f, sink));
 		} else {
 			log.s += "Error: file format not recognized.\n";
 			*mode = PGX_TRIM_UNKNOWN;

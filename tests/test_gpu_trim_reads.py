@@ -176,6 +176,23 @@ def test_irregular_records_take_the_text_route(pg, tmp_path, what, a, b, opts):
     assert len(got) > 0
 
 
+def text_route_at_size():
+    fq = fastq_text(12, 700, 20, 160) + _fq([("odd", ">" + GOOD, "I" * 101)])
+    yield "fastq interleaved, 351 records", fq, b"", {"g": "7"}, 300
+    a, b = qseq_text(13, 600, 10, 300)
+    yield "qseq, 601 pairs", a + b"HWI-X\t12\t1\r\n", b + _qs("x", 2, GOOD, "h" * 100).encode(), {"g": "100"}, 0
+
+
+@pytest.mark.parametrize("what,a,b,opts,more_than", list(text_route_at_size()), ids=[c[0] for c in text_route_at_size()])
+def test_the_text_route_past_one_block(pg, tmp_path, what, a, b, opts, more_than):
+    """The inputs of test_fastq_interleaved and test_qseq_pairs with one irregular record behind them (a sequence line that
+    begins with '>'; a short -a line that ends in a carriage return): the text route with more records than one block of a
+    measure kernel (256) or of a writer (16 lane groups) takes, where the raw text and the columns are let go before the
+    FASTA is split.  The oracle prints 351 records for the FASTQ input."""
+    want, got, _ = check(pg, tmp_path, pg.TRIM_ROUTE_TEXT, a, b, **opts)
+    assert len(got) > more_than
+
+
 def test_the_regular_twins_take_the_packed_route(pg, tmp_path):
     """The same shapes without the one odd record or byte: packed.  (Blanks and tabs inside a kept span, a '>' that is not
     the first byte of the line, a header with '@' and without a blank are all regular.)"""
