@@ -21,9 +21,10 @@
 // k_scan_*, k_scatter_hits, k_merge_pieces
 //                 per-read offsets of the table; only fragmented reads are moved.
 // k_sort_consensus<32 / 64>
-//                 one wavefront per two reads of up to 32 hits, then per read of 33-64: one hit per lane, keys in LDS, the
-//                 best score of a hit's subject, spec S3c (duplicate alignments of one subject), the rank by counting, the
-//                 ordered rows written out, then the (rank,name) agreement with the read's RDP assignment per hit and the
+//                 one wavefront per two reads of up to 32 hits, then per read of 33-64: one hit per lane, one pass over
+//                 (subject, score) rows in LDS for the best score of a hit's subject and the rank by counting; only where a
+//                 read has two hits on one subject the full keys in LDS, spec S3c (duplicate alignments of one subject)
+//                 and the rank on the keys; the ordered rows written out, then the (rank,name) agreement with the read's RDP assignment per hit and the
 //                 order-dependent arg-max of the Perl with its string comparisons as two reductions (a chain walk when
 //                 lineages differ in depth).  Reads with more hits: bigreads.hip.
 #include <algorithm>
@@ -1362,14 +1363,14 @@ __device__ __forceinline__ SortKey make_key(const pgx_hit &h, int best)
 	return k;
 }
 
-// LDS of one wave.  Phase A holds (subject, score) pairs then the sort keys; phase B (after every lane has
+// LDS of one wave.  Phase A holds (subject, score) rows and, where a subject repeats, the sort keys; phase B (after every lane has
 // its rank) reuses the same bytes for the per-rank consensus inputs.  3 KB per wave keeps the kernel at the
 // register-limited occupancy: it is bound by the latency of its gathers, not by arithmetic.
 struct SortWave {
 	union {
 		struct {
 			uint64_t k1[kSortCap], k2[kSortCap];
-			int subj[kSortCap], score[kSortCap];
+			uint64_t row[kSortCap]; // order_row(subject, score)
 			uint32_t send[kSortCap], mg[kSortCap];
 		} a;
 		struct {
@@ -1383,6 +1384,92 @@ struct SortWave {
 	uint32_t rcode[2][kRdpRegs]; // the RDP codes of the wave's (up to) two reads: fetched one per lane at the top of a round, read
 				     // back when the ranks are known -- eight registers per lane less through the ranking loops
 };
+
+// One row of the ranking pass: score above the complemented subject, so that one unsigned compare says "higher score, or
+// the same score and a smaller subject" (scores are positive).  A real hit's low word is never zero: subjects are < 2^31.
+__device__ __forceinline__ uint64_t order_row(int subject, int score)
+{
+	return ((uint64_t)(uint32_t)score << 32) | (uint64_t)~(uint32_t)subject;
+}
+
+// The ranking of a wavefront in which a read has two hits on one subject: the full S5 keys through LDS, S3c, the count on
+// the first key word and the tie pass.  Returns the lane's rank; `*n` becomes the number of hits kept (written to
+// `*cnt_out` when hits were dropped), `*dropped_out` whether S3c dropped this lane's hit.
+template <int G>
+__device__ __forceinline__ uint32_t rank_repeated_subjects(SortWave *sw, const pgx_hit &h, int best, bool mine, int li, int slot0, int lane,
+							unsigned long long grp_mask, uint32_t nmax, uint32_t *n_io, bool *dropped_out,
+							uint32_t *cnt_out)
+{
+	uint32_t n = *n_io;
+	const SortKey kx = make_key(h, best);
+	sw->a.k1[slot0 + li] = mine ? kx.k1 : ~0ull; // (past the end: a key that precedes none and equals none)
+	if (mine) {
+		sw->a.k2[slot0 + li] = kx.k2;
+		sw->a.send[slot0 + li] = kx.send;
+		sw->a.mg[slot0 + li] = kx.mg;
+	}
+	lds_fence();
+	// Spec v2, S3c: hits of one subject that describe the same alignment (the seeds on either side of a gap all grow
+	// into it).  A hit is dropped when a hit BEFORE it in the S5 order, on the same subject and strand, starts at the
+	// same point, ends at the same point, or holds it.
+	bool dropped = false;
+	{
+		const uint32_t my_s0 = (uint32_t)(h.send > h.sstart ? h.sstart : h.send), my_s1 = (uint32_t)(h.send > h.sstart ? h.send : h.sstart);
+		for (uint32_t j = 0; j < nmax; j++) {
+			const uint32_t sl = slot0 + (j & (G - 1));
+			const uint64_t b1 = sw->a.k1[sl], b2 = sw->a.k2[sl];
+			const uint32_t bsend = sw->a.send[sl], bmg = sw->a.mg[sl];
+			const bool before = (b1 < kx.k1) | ((b1 == kx.k1) & ((b2 < kx.k2) | ((b2 == kx.k2) & ((bsend < kx.send) | ((bsend == kx.send) &
+					    ((bmg < kx.mg) | ((bmg == kx.mg) & (j < (uint32_t)li))))))));
+			const bool same = (uint32_t)(b1 >> 16) == (uint32_t)h.subject && ((b2 ^ kx.k2) & 1ull) == 0ull;
+			const uint32_t bq0 = (uint32_t)(b2 >> 48), bq1 = (uint32_t)(b2 >> 32) & 0xFFFFu, bsst = (uint32_t)(b2 >> 1) & 0x7FFFFFFFu;
+			const uint32_t bs0 = bsend > bsst ? bsst : bsend, bs1 = bsend > bsst ? bsend : bsst;
+			const bool dup = (bq0 == (uint32_t)h.qstart && bsst == (uint32_t)h.sstart) || (bq1 == (uint32_t)h.qend && bsend == (uint32_t)h.send) ||
+					 ((uint32_t)h.qstart >= bq0 && (uint32_t)h.qend <= bq1 && my_s0 >= bs0 && my_s1 <= bs1);
+			dropped |= (j < n) & before & same & dup;
+		}
+	}
+	const unsigned long long drop_mask = __ballot(mine && dropped);
+	const uint32_t n_drop = (uint32_t)__popcll(drop_mask & grp_mask);
+	const uint32_t n_all = n; // slots of the read; n becomes the hits that are kept
+	const bool kept = mine && !dropped;
+	if (n_drop) {
+		n -= n_drop;
+		if (li == 0)
+			*cnt_out = n;
+	}
+	// rank = number of kept hits that precede this one.  Nearly every pair differs in the first key word (best
+	// score, subject, score): count on that word alone, and compare second words only inside groups of equal
+	// first words (several HSPs of one subject with one score).
+	uint32_t rank = 0, same = 0;
+	for (uint32_t j0 = 0; j0 < nmax; j0 += 4) {
+		uint64_t a1[4];
+#pragma unroll
+		for (int u = 0; u < 4; u++)
+			a1[u] = sw->a.k1[slot0 + ((j0 + u) & (G - 1))];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			const bool in = (j0 + u < n_all) & !((drop_mask >> (slot0 + ((j0 + u) & (G - 1)))) & 1ull);
+			rank += (in & (a1[u] < kx.k1)) ? 1u : 0u;
+			same += (in & (a1[u] == kx.k1)) ? 1u : 0u;
+		}
+	}
+	if (__ballot(kept && same > 1u)) {
+		for (uint32_t j = 0; j < nmax; j++) {
+			const uint32_t sl = slot0 + (j & (G - 1));
+			const uint64_t b1 = sw->a.k1[sl], b2 = sw->a.k2[sl];
+			const uint32_t bsend = sw->a.send[sl], bmg = sw->a.mg[sl];
+			const bool before = (b1 == kx.k1) & ((b2 < kx.k2) | ((b2 == kx.k2) & ((bsend < kx.send) | ((bsend == kx.send) &
+					    ((bmg < kx.mg) | ((bmg == kx.mg) & (j < (uint32_t)li)))))));
+			rank += (before & (j < n_all) & !((drop_mask >> sl) & 1ull)) ? 1u : 0u;
+		}
+	}
+	if (dropped) // dropped hits keep the slots behind the kept ones (the table stays initialised)
+		rank = n + (uint32_t)__popcll(drop_mask & grp_mask & ((1ull << lane) - 1ull));
+	*n_io = n;
+	*dropped_out = dropped;
+	return rank;
+}
 
 // G lanes per read: G = 32 orders two reads per wavefront (most reads have <= 32 hits), G = 64 one.  A read with
 // more than G hits is passed on through `next_list` (to the G = 64 launch, then to the big-read path).
@@ -1477,8 +1564,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 8) void k_sort_consensus(pgx_h
 		if (mine)
 			h = src[li];
 		// (rows past the read's end hold a subject no hit has, so the loops below need no "j < n" of their own)
-		sw->a.subj[slot0 + li] = mine ? h.subject : -1;
-		sw->a.score[slot0 + li] = h.score;
+		sw->a.row[slot0 + li] = mine ? order_row(h.subject, h.score) : 0ull;
 		if (li < kRdpRegs)
 			sw->rcode[g][li] = my_code;
 		lds_fence();
@@ -1487,28 +1573,31 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 8) void k_sort_consensus(pgx_h
 				hits[o + li] = h;
 			continue;
 		}
-		// best score of the hit's subject.  Loops run a wave-uniform number of rounds, four LDS rows in
-		// flight per round; rows past a read's end (stale bytes) are masked by j < n.
+		// One pass over the read's rows gives the best score of the hit's subject, the number of hits on that subject
+		// and the hit's rank when no subject repeats: then best == score for every hit, the first key word
+		// (best desc, subject asc, score desc) orders by score and subject alone, and the rank is the number of rows
+		// with a higher score, or the same score and a smaller (unsigned) subject -- one 64-bit compare of the row
+		// words.  Loops run a wave-uniform number of rounds, four LDS rows in flight per round; rows past a read's end
+		// hold zero, which precedes no hit and equals no hit's subject.
 		const uint32_t nmax = RPW == 2 ? max(__shfl(n, 0), __shfl(n, 32)) : n;
+		const uint64_t my_row = order_row(h.subject, h.score);
 		int best = h.score;
 		uint32_t same_subj = 0; // hits of this read on the hit's subject (itself included)
+		uint32_t rank = 0;      // number of hits that precede this one
 		for (uint32_t j0 = 0; j0 < nmax; j0 += 4) {
-			int sj[4], sc[4];
-#pragma unroll
-			for (int u = 0; u < 4; u++) {
-				sj[u] = sw->a.subj[slot0 + ((j0 + u) & (G - 1))];
-				sc[u] = sw->a.score[slot0 + ((j0 + u) & (G - 1))];
-			}
+			uint64_t row[4];
 #pragma unroll
 			for (int u = 0; u < 4; u++)
-				if (sj[u] == h.subject) {
+				row[u] = sw->a.row[slot0 + ((j0 + u) & (G - 1))];
+#pragma unroll
+			for (int u = 0; u < 4; u++) {
+				rank += row[u] > my_row ? 1u : 0u;
+				if ((uint32_t)row[u] == (uint32_t)my_row) {
 					same_subj++;
-					if (sc[u] > best)
-						best = sc[u];
+					best = max(best, (int)(row[u] >> 32));
 				}
+			}
 		}
-		const SortKey kx = make_key(h, best);
-		lds_fence();
 		if (PGX_SORT_DBG(cv) == 2) {
 			if (mine) {
 				h.score = best;
@@ -1516,85 +1605,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 8) void k_sort_consensus(pgx_h
 			}
 			continue;
 		}
-		sw->a.k1[slot0 + li] = mine ? kx.k1 : ~0ull; // (past the end: a key that precedes none and equals none)
-		if (mine) {
-			sw->a.k2[slot0 + li] = kx.k2;
-			sw->a.send[slot0 + li] = kx.send;
-			sw->a.mg[slot0 + li] = kx.mg;
-		}
-		lds_fence();
-		// Spec v2, S3c: hits of one subject that describe the same alignment (the seeds on either side of a gap all grow
-		// into it).  A hit is dropped when a hit BEFORE it in the S5 order, on the same subject and strand, starts at the
-		// same point, ends at the same point, or holds it.  Only reads with two hits on one subject look (wave-uniform).
-		bool dropped = false;
-		if (__ballot(mine && same_subj > 1u)) {
-			const uint32_t my_s0 = (uint32_t)(h.send > h.sstart ? h.sstart : h.send), my_s1 = (uint32_t)(h.send > h.sstart ? h.send : h.sstart);
-			for (uint32_t j = 0; j < nmax; j++) {
-				const uint32_t sl = slot0 + (j & (G - 1));
-				const uint64_t b1 = sw->a.k1[sl], b2 = sw->a.k2[sl];
-				const uint32_t bsend = sw->a.send[sl], bmg = sw->a.mg[sl];
-				const bool before = (b1 < kx.k1) | ((b1 == kx.k1) & ((b2 < kx.k2) | ((b2 == kx.k2) & ((bsend < kx.send) | ((bsend == kx.send) &
-						    ((bmg < kx.mg) | ((bmg == kx.mg) & (j < (uint32_t)li))))))));
-				const bool same = (uint32_t)(b1 >> 16) == (uint32_t)h.subject && ((b2 ^ kx.k2) & 1ull) == 0ull;
-				const uint32_t bq0 = (uint32_t)(b2 >> 48), bq1 = (uint32_t)(b2 >> 32) & 0xFFFFu, bsst = (uint32_t)(b2 >> 1) & 0x7FFFFFFFu;
-				const uint32_t bs0 = bsend > bsst ? bsst : bsend, bs1 = bsend > bsst ? bsend : bsst;
-				const bool dup = (bq0 == (uint32_t)h.qstart && bsst == (uint32_t)h.sstart) || (bq1 == (uint32_t)h.qend && bsend == (uint32_t)h.send) ||
-						 ((uint32_t)h.qstart >= bq0 && (uint32_t)h.qend <= bq1 && my_s0 >= bs0 && my_s1 <= bs1);
-				dropped |= (j < n) & before & same & dup;
-			}
-		}
-		const unsigned long long drop_mask = __ballot(mine && dropped);
 		const unsigned long long grp_mask = G == 64 ? ~0ull : (g ? 0xFFFFFFFF00000000ull : 0x00000000FFFFFFFFull);
-		const uint32_t n_drop = (uint32_t)__popcll(drop_mask & grp_mask);
-		const uint32_t n_all = n; // slots of the read; n becomes the hits that are kept
+		bool dropped = false;
+		// Only a wavefront with a read that has two hits on one subject (wave-uniform; about one in a thousand on the
+		// bench batch) builds the sort keys: S3c may drop a hit, `best` can move a subject's lower row ahead of another
+		// subject's, and equal first key words need the later ones.  Both reads of a G = 32 wavefront share the route.
+		if (__ballot(mine && same_subj > 1u))
+			rank = rank_repeated_subjects<G>(sw, h, best, mine, li, slot0, lane, grp_mask, nmax, &n, &dropped, read_cnt + r);
 		const bool kept = mine && !dropped;
-		if (n_drop) {
-			n -= n_drop;
-			if (li == 0)
-				read_cnt[r] = n;
-		}
-		// rank = number of hits that precede this one.  Nearly every pair differs in the first key word (best
-		// score, subject, score): count on that word alone, and compare second words only inside groups of equal
-		// first words (several HSPs of one subject with one score), which most reads do not have.
-		uint32_t rank = 0, same = 0;
-		if (drop_mask == 0ull) { // the usual wavefront: nothing was dropped, rows past a read's end hold the last key
-			for (uint32_t j0 = 0; j0 < nmax; j0 += 4) {
-				uint64_t a1[4];
-#pragma unroll
-				for (int u = 0; u < 4; u++)
-					a1[u] = sw->a.k1[slot0 + ((j0 + u) & (G - 1))];
-#pragma unroll
-				for (int u = 0; u < 4; u++) {
-					rank += a1[u] < kx.k1 ? 1u : 0u;
-					same += a1[u] == kx.k1 ? 1u : 0u;
-				}
-			}
-		} else {
-			for (uint32_t j0 = 0; j0 < nmax; j0 += 4) {
-				uint64_t a1[4];
-#pragma unroll
-				for (int u = 0; u < 4; u++)
-					a1[u] = sw->a.k1[slot0 + ((j0 + u) & (G - 1))];
-#pragma unroll
-				for (int u = 0; u < 4; u++) {
-					const bool in = (j0 + u < n_all) & !((drop_mask >> (slot0 + ((j0 + u) & (G - 1)))) & 1ull);
-					rank += (in & (a1[u] < kx.k1)) ? 1u : 0u;
-					same += (in & (a1[u] == kx.k1)) ? 1u : 0u;
-				}
-			}
-		}
-		if (__ballot(kept && same > 1u)) {
-			for (uint32_t j = 0; j < nmax; j++) {
-				const uint32_t sl = slot0 + (j & (G - 1));
-				const uint64_t b1 = sw->a.k1[sl], b2 = sw->a.k2[sl];
-				const uint32_t bsend = sw->a.send[sl], bmg = sw->a.mg[sl];
-				const bool before = (b1 == kx.k1) & ((b2 < kx.k2) | ((b2 == kx.k2) & ((bsend < kx.send) | ((bsend == kx.send) &
-						    ((bmg < kx.mg) | ((bmg == kx.mg) & (j < (uint32_t)li)))))));
-				rank += (before & (j < n_all) & !((drop_mask >> sl) & 1ull)) ? 1u : 0u;
-			}
-		}
-		if (dropped) // dropped hits keep the slots behind the kept ones (the table stays initialised)
-			rank = n + (uint32_t)__popcll(drop_mask & grp_mask & ((1ull << lane) - 1ull));
 		if (mine)
 			store_hit_stream(hits + o + rank, h);
 		if (!do_consensus || PGX_SORT_DBG(cv) == 3)
