@@ -359,6 +359,29 @@ int pgx_megaclust_batch(const pgx_db *db, const pgx_reads *reads, const pgx_hits
  * script's @ARGV (no program name).  Byte-identical output file; `log_text` = its stdout. */
 int pgx_megaclustable(int argc, const char *const *argv, char **log_text);
 
+/* ---- the reads Classify left without a good hit ------------------------------------------------
+ * Unclas_Sel/unclassified_selector.pl:21-169 `-m table.tsv -s reads.fas -o out.fas [-t PCT] [-e LN_EVALUE] [-b BITS]`:
+ * argv is the script's @ARGV (no program name), walked as the script walks it (:32-59: positions 0..11, values included).
+ * A table row passes when !(pident < t || evalue > exp(e) || bits < b) on Perl-numified columns (:96; defaults 95, -20,
+ * 200); a read name is classified when one of its rows passes; the output is the FASTA without the FIRST record of every
+ * classified name (:126-166), each printed header as ">name \n" with name = the whole header line behind its first
+ * character.  Byte-identical output file; `log_text` = its stdout.  An `-o` that cannot be created (the script dies with
+ * $!, :123) returns PGX_E_IO with the stdout printed so far. */
+int pgx_unclas_file(int argc, const char *const *argv, char **log_text);
+/* The same selection on a resident batch and its hit table (`hits` = the table of a search of `reads` through `db`):
+ * mask_out[r] = 1 exactly for the reads pgx_unclas_file prints when given pgx_hits_format's text of `hits` and
+ * pgx_reads_write_fasta's text of `reads`; `out` = the batch pgx_reads_from_fasta_text makes of that output, same order
+ * (names, ambiguity words, pieces, DUST bits and search classes included), built in HBM from the packed bases.  The
+ * thresholds are exact integer images of the text comparisons (hundredths of pident, lowest raw score per read length), as
+ * in pgx_megaclust_batch, and follow the table's own gapped / ungapped statistics.  Option texts as @ARGV holds them
+ * (NULL = the script's default; `o` may be NULL).  mask_out (cap >= number of reads) and out may be NULL; n_selected is
+ * always set.  Runs on the handle's stream under the handle's lock. */
+typedef struct {
+	const char *t, *e, *b;
+} pgx_unclas_opts;
+int pgx_unclassified_batch(pgx_db *db, const pgx_reads *reads, const pgx_hits *hits, const pgx_unclas_opts *o, uint8_t *mask_out,
+			   int64_t cap, int64_t *n_selected, pgx_reads **out);
+
 /* Columns 11-12 (e-value, bit score) of a `blastn -outfmt 6` row (README.md:96) for a raw score, as the row formatter
  * prints them: lambda 1.28, K 0.46 (reward 1 / penalty -2), BLAST+ tabular number formats.  Host arithmetic only.
  * The reference's only record of its BLAST dependency's output, validation_dataset/Data-set_2_consensus.xlsx

@@ -2,6 +2,7 @@
 import ctypes as C
 import os
 import sys
+import threading
 
 import numpy as np
 
@@ -97,7 +98,7 @@ SYMBOLS = [
     "pgx_reads_get", "pgx_reads_get_dust", "pgx_db_get_dust", "pgx_blast_search", "pgx_hits_close", "pgx_hits_count", "pgx_hits_copy",
     "pgx_hits_read_offsets", "pgx_hits_read_counts", "pgx_hits_slice", "pgx_hits_format", "pgx_db_bind_taxonomy", "pgx_db_subject_lineage",
     "pgx_rdp_from_file", "pgx_rdp_from_synth", "pgx_rdp_close", "pgx_consensus_batch", "pgx_classify_consensus", "pgx_classify_consensus_tri", "pgx_vote3_batch", "pgx_vote3_format",
-    "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_trim_file", "pgx_trim_reads", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
+    "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_unclas_file", "pgx_unclassified_batch", "pgx_trim_file", "pgx_trim_reads", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
 ]
 
 
@@ -144,6 +145,8 @@ def _declare(L):
     sig("pgx_megaclust_file", C.c_int, [V, V])
     sig("pgx_megaclust_batch", C.c_int, [V, V, V, V, I64, V, V, V, V])
     sig("pgx_megaclustable", C.c_int, [C.c_int, V, V])
+    sig("pgx_unclas_file", C.c_int, [C.c_int, V, V])
+    sig("pgx_unclassified_batch", C.c_int, [V, V, V, V, V, I64, V, V])
     sig("pgx_trim_file", C.c_int, [V, V, V, V, V])
     sig("pgx_trim_reads", C.c_int, [V, V, V, V, V])
     sig("pgx_probe_gather", C.c_int, [C.c_uint64, C.c_int, V, V])
@@ -608,6 +611,52 @@ def megaclustable(argv):
     text = _take_text(log.value)
     _check(rc)
     return text
+
+
+_cwd_lock = threading.Lock()
+
+
+def unclassified_selector(argv, cwd=None):
+    """`perl Unclas_Sel/unclassified_selector.pl -m TABLE -s READS.fas -o OUT [-t PCT] [-e LN_EVALUE] [-b BITS]`; `argv` is
+    the word list after the script name, `cwd` the directory its file names are relative to (the messages echo the names as
+    given, so they are not rewritten: the call changes the process's directory for its duration).  Returns the script's
+    stdout; an -o file that cannot be created raises PangeaError (status -2) with the stdout so far as its `stdout`."""
+    words = [os.fsencode(str(w)) for w in argv]
+    arr = (C.c_char_p * max(1, len(words)))(*words)
+    log = C.c_void_p()
+    with _cwd_lock:
+        back = os.getcwd() if cwd is not None else None
+        if cwd is not None:
+            os.chdir(cwd)
+        try:
+            rc = lib().pgx_unclas_file(len(words), arr, C.byref(log))
+        finally:
+            if back is not None:
+                os.chdir(back)
+    text = _take_text(log.value)
+    if rc < 0:
+        err = PangeaError(rc, lib().pgx_last_error().decode("utf-8", "replace"))
+        err.stdout = text
+        raise err
+    return text
+
+
+class _UnclasOpts(C.Structure):
+    _fields_ = [("t", C.c_char_p), ("e", C.c_char_p), ("b", C.c_char_p)]
+
+
+def unclassified(db, reads, hits, t=None, e=None, b=None, want_reads=True):
+    """The reads of a resident batch that unclassified_selector would print for its table `hits` (option texts as on the
+    command line; None = the script's default: 95, -20, 200): (mask uint8[n], Reads of the selected ones or None)."""
+    txt = lambda v: None if v is None else str(v).encode()  # noqa: E731
+    o = _UnclasOpts(txt(t), txt(e), txt(b))
+    n = len(reads)
+    mask = np.zeros(n, dtype=np.uint8)
+    n_sel, p = C.c_int64(), C.c_void_p()
+    _check(lib().pgx_unclassified_batch(db.ptr, reads.ptr, hits.ptr, C.byref(o), mask.ctypes.data if n else None, n, C.byref(n_sel),
+                                        C.byref(p) if want_reads else None))
+    assert int(mask.sum()) == n_sel.value
+    return mask, (Reads(p) if want_reads else None)
 
 
 def blast_score_columns(score, qlen, db_len, db_nseq, gapped=True):

@@ -2011,6 +2011,14 @@ static int workspace_of(pgx_db *db, Workspace **out)
 	return 0;
 }
 
+int db_stream(pgx_db *db, hipStream_t *out)
+{
+	Workspace *ws = nullptr;
+	PGX_TRY(workspace_of(db, &ws));
+	*out = ws->stream;
+	return 0;
+}
+
 // search + gapped stage + group + order (+ consensus when rdp != null). d_recs: device array of n_reads records.
 int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out, pgx_consensus_rec *d_recs)
 {

@@ -225,6 +225,17 @@ int device_line_index(const uint8_t *d_text, uint64_t n, bool open_tail, DevBuf<
 // the RDP table of a batch parsed on the device; 1 = this form does not apply to the batch (the caller takes the host form)
 int rdp_from_text_device(const char *text, size_t n_bytes, const pgx_reads *reads, pgx_db *db, pgx_rdp **out);
 
+// megaclust.hip
+struct RowThresholds {
+	int h_min = 10001;           // lowest passing pident, in hundredths
+	uint32_t max_len = 0;        // s_min has max_len + 1 entries
+	std::vector<uint32_t> s_min; // per read length: the lowest passing raw score (0xFFFFFFFF: none passes)
+};
+void row_thresholds(double sim, double ev_max, double bits_min, const pgx_db *db, const pgx_reads *reads, int64_t n, bool gapped,
+		    RowThresholds &out);
+int filter_lines_device(const double *d_pid, const double *d_ev, const double *d_bits, uint64_t n, double sim, double ev_max,
+			double bits_min, uint8_t *d_pass, hipStream_t stream);
+
 // dust.hip
 int reads_dust(pgx_reads *rd);
 int reads_dust_again(const pgx_reads *rd, DustBufs &b, hipStream_t stream);
@@ -237,6 +248,8 @@ struct SearchCounters {
 	unsigned long long probes, postings, candidates, hits;
 };
 int blast_search_device(pgx_db *db, pgx_reads *reads, pgx_hits *out, pgx_stage_times *times);
+// the stream of the handle's searches, made on first use; the caller holds db->search_mu
+int db_stream(pgx_db *db, hipStream_t *out);
 int consensus_device(const pgx_db *db, const pgx_hits *hits, const pgx_rdp *rdp, pgx_consensus_rec *d_out,
 		     pgx_stage_times *times);
 

@@ -17,56 +17,11 @@
 #include <map>
 
 #include "engine.hpp"
+#include "perlops.hpp"
 
 namespace pgx {
 
 void format_score_columns(int score, int64_t qlen, int64_t db_len, int64_t db_nseq, bool gapped, std::string &evalue, std::string &bits);
-
-// ------------------------------------------------------------------------------------------ Perl semantics (host)
-static inline bool p_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\f' || c == '\v'; }
-
-// what `<`, `>` and `+=` make of a string (perlnumber): optional blanks and sign, Inf/NaN, decimal digits
-// with optional fraction and exponent; anything else counts as 0, trailing text is ignored
-double perl_num(const char *s, size_t n)
-{
-	size_t i = 0;
-	while (i < n && p_space(s[i]))
-		i++;
-	const size_t st = i;
-	if (i < n && (s[i] == '+' || s[i] == '-'))
-		i++;
-	auto low = [&](size_t k) { return k < n ? (char)tolower((unsigned char)s[k]) : '\0'; };
-	if (low(i) == 'i' && low(i + 1) == 'n' && low(i + 2) == 'f')
-		return s[st] == '-' ? -INFINITY : INFINITY;
-	if (low(i) == 'n' && low(i + 1) == 'a' && low(i + 2) == 'n')
-		return NAN;
-	size_t nd = 0;
-	while (i < n && isdigit((unsigned char)s[i]))
-		i++, nd++;
-	if (i < n && s[i] == '.') {
-		i++;
-		while (i < n && isdigit((unsigned char)s[i]))
-			i++, nd++;
-	}
-	if (nd == 0)
-		return 0.0;
-	if (i < n && (s[i] == 'e' || s[i] == 'E')) {
-		size_t j = i + 1;
-		if (j < n && (s[j] == '+' || s[j] == '-'))
-			j++;
-		if (j < n && isdigit((unsigned char)s[j])) {
-			while (j < n && isdigit((unsigned char)s[j]))
-				j++;
-			i = j;
-		}
-	}
-	std::string t(s + st, i - st);
-	return strtod(t.c_str(), nullptr);
-}
-static double perl_num(const std::string &s) { return perl_num(s.data(), s.size()); }
-
-// Perl truth of an option value: undef, "" and "0" are false
-bool perl_true(const char *v) { return v && v[0] && !(v[0] == '0' && v[1] == 0); }
 
 struct Field {
 	const char *p;
@@ -169,6 +124,65 @@ __global__ void k_mc_filter_lines(const double *__restrict__ pid, const double *
 	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n)
 		pass[i] = !(pid[i] < sim || ev[i] > ev_max || bits[i] < bits_min);
+}
+
+// The three text comparisons a script makes on a printed -outfmt 6 row (`!(pident < sim || evalue > ev_max || bits <
+// bits_min)` on numified texts), as integer tests on the row's record: `hundredths >= h_min && score >= s_min[read
+// length]`, for the lengths of reads [0, n) of the batch.  The pident text is "%.2f" of hundredths / 100; the e-value and
+// bit-score texts are functions of (raw score, read length), and the accepted scores form an upper range (E falls and the
+// bit score rises with the score, the formats are monotone).  Shared by pgx_megaclust_batch and pgx_unclassified_batch.
+void row_thresholds(double sim, double ev_max, double bits_min, const pgx_db *db, const pgx_reads *reads, int64_t n, bool gapped,
+		    RowThresholds &out)
+{
+	int h_min = 10001;
+	for (int h = 0; h <= 10000; h++) {
+		char buf[16];
+		snprintf(buf, sizeof buf, "%d.%02d", h / 100, h % 100);
+		if (!(perl_num(buf, strlen(buf)) < sim)) {
+			h_min = h;
+			break;
+		}
+	}
+	const uint32_t max_len = (uint32_t)reads->max_len;
+	std::vector<uint32_t> s_min((size_t)max_len + 1, 0xFFFFFFFFu);
+	std::vector<uint8_t> seen((size_t)max_len + 1, 0);
+	for (int64_t r = 0; r < n; r++)
+		seen[reads->h_len[(size_t)r]] = 1;
+	std::string evt, bst;
+	auto ok_score = [&](int score, uint32_t L) {
+		format_score_columns(score, L, db->n_bases, db->n_seq, gapped, evt, bst);
+		return !(perl_num(evt) > ev_max) && !(perl_num(bst) < bits_min);
+	};
+	for (uint32_t L = 0; L <= max_len; L++) {
+		if (!seen[L] || L == 0)
+			continue;
+		if (!ok_score((int)L, L))
+			continue; // not even a full-length perfect match passes
+		int lo = 0, hi = (int)L; // hi passes; lowest passing score by bisection
+		while (lo < hi) {
+			const int mid = lo + (hi - lo) / 2;
+			if (ok_score(mid, L))
+				hi = mid;
+			else
+				lo = mid + 1;
+		}
+		s_min[L] = (uint32_t)hi;
+	}
+	out.h_min = h_min;
+	out.max_len = max_len;
+	out.s_min = std::move(s_min);
+}
+
+// k_mc_filter_lines on `stream`, for the other script drop-ins whose rows carry the same three columns (unclas.hip)
+int filter_lines_device(const double *d_pid, const double *d_ev, const double *d_bits, uint64_t n, double sim, double ev_max,
+			double bits_min, uint8_t *d_pass, hipStream_t stream)
+{
+	if (n == 0)
+		return 0;
+	hipLaunchKernelGGL(k_mc_filter_lines, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_pid, d_ev, d_bits, n, sim, ev_max,
+			   bits_min, d_pass);
+	PGX_HIP(hipGetLastError());
+	return 0;
 }
 
 // Batch form: one consensus record per read.  A winner's printed columns are functions of integers:
@@ -352,28 +366,6 @@ __global__ void k_pivot_cells(const uint32_t *__restrict__ cell_off, const doubl
 	sum[c] = s;
 }
 
-static long p_index(const std::string &s, const std::string &sub, long pos)
-{
-	if (pos < 0)
-		pos = 0;
-	if ((size_t)pos > s.size())
-		pos = (long)s.size();
-	const size_t r = s.find(sub, (size_t)pos);
-	return r == std::string::npos ? -1 : (long)r;
-}
-// substr(str, off, len), off >= 0; a negative len leaves that many characters off the end
-static std::string p_substr(const std::string &s, long off, long len)
-{
-	if (off < 0 || (size_t)off > s.size())
-		return std::string();
-	long end = len >= 0 ? off + len : (long)s.size() + len;
-	if (end > (long)s.size())
-		end = (long)s.size();
-	if (end <= off)
-		return std::string();
-	return s.substr((size_t)off, (size_t)(end - off));
-}
-
 static std::string perl_number_text(double v)
 {
 	char buf[64];
@@ -476,45 +468,11 @@ int pgx_megaclust_batch(const pgx_db *db, const pgx_reads *reads, const pgx_hits
 		// OTU ids come with the taxonomy binding: one per distinct lineage text, plus one for the empty text
 		const std::vector<std::string> &lin_text = db->lin_text;
 		const uint32_t empty_lin = db->empty_lin;
-		// thresholds as integers.  pident: the text is "%.2f" of hundredths / 100
-		int h_min = 10001;
-		for (int h = 0; h <= 10000; h++) {
-			char buf[16];
-			snprintf(buf, sizeof buf, "%d.%02d", h / 100, h % 100);
-			if (!(perl_num(buf, strlen(buf)) < p.sim)) {
-				h_min = h;
-				break;
-			}
-		}
-		// e-value and bit score: both texts are functions of (raw score, read length); accepted scores form an
-		// upper range (E falls and the bit score rises with the score, the formats are monotone)
-		const uint32_t max_len = (uint32_t)reads->max_len;
-		std::vector<uint32_t> s_min((size_t)max_len + 1, 0xFFFFFFFFu);
-		{
-			std::vector<uint8_t> seen((size_t)max_len + 1, 0);
-			for (int64_t r = 0; r < n; r++)
-				seen[reads->h_len[(size_t)r]] = 1;
-			std::string evt, bst;
-			auto ok_score = [&](int score, uint32_t L) {
-				format_score_columns(score, L, db->n_bases, db->n_seq, hits->gapped, evt, bst);
-				return !(perl_num(evt) > p.ev) && !(perl_num(bst) < p.bits);
-			};
-			for (uint32_t L = 0; L <= max_len; L++) {
-				if (!seen[L] || L == 0)
-					continue;
-				if (!ok_score((int)L, L))
-					continue; // not even a full-length perfect match passes
-				int lo = 0, hi = (int)L; // hi passes; lowest passing score by bisection
-				while (lo < hi) {
-					const int mid = lo + (hi - lo) / 2;
-					if (ok_score(mid, L))
-						hi = mid;
-					else
-						lo = mid + 1;
-				}
-				s_min[L] = (uint32_t)hi;
-			}
-		}
+		RowThresholds th;
+		row_thresholds(p.sim, p.ev, p.bits, db, reads, n, hits->gapped, th);
+		const int h_min = th.h_min;
+		const uint32_t max_len = th.max_len;
+		const std::vector<uint32_t> &s_min = th.s_min;
 		const int empty_pass = !(0.0 < p.sim || 0.0 > p.ev || 0.0 < p.bits);
 		// query texts: a pair (OTU, query) counts once; only repeated read names need the key sort
 		bool unique_queries = true;

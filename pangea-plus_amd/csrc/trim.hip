@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "engine.hpp"
+#include "perlops.hpp"
 #include "textops.hpp"
 
 namespace pgx {
