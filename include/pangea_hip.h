@@ -113,6 +113,11 @@ int pgx_db_set_dust(pgx_db *db, int dust); /* 1 (default): DUST-masked bases of 
  * first stage -- query masking as `blastn` runs it, inside the search (reference README.md:96); 0 (default): the bits made
  * when the batch was imported are used (the same bits: they depend on the reads alone) */
 int pgx_db_set_dust_each_search(pgx_db *db, int on);
+/* The seed stage of a search walks its reads in the order of the database region their first 16-mers point at, so that the
+ * database lines a region's reads want are fetched once (results do not depend on it: every output is addressed by the
+ * read's number).  mode 0 (default): automatic -- search classes of four million reads and more against databases of 128 Mbp
+ * and more; 1: every class of every search; 2: never.  The order is made inside each search and kept nowhere. */
+int pgx_db_set_read_order(pgx_db *db, int mode);
 
 /* ------------------------------------------------------------------------------------------
  * Classify, SOAP verb  —  `soap -a reads -D ref.index -o out -p 8 -M 4` (README.md:134;
@@ -249,6 +254,11 @@ int pgx_reads_get_dust(const pgx_reads *r, uint8_t *any_out, uint32_t *woff_out,
 		       uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out);
 int pgx_db_get_dust(pgx_db *db, const pgx_reads *r, uint8_t *any_out, uint32_t *woff_out, uint64_t *mask_out, uint64_t *win_f_out,
 		    uint64_t *win_r_out, int64_t cap_words, int64_t *n_words_out);
+/* For tests: the list the last search through `db` walked and its keys.  `r` is the batch that search was given.  n_out: the
+ * entries (0: no class was ordered); order_out / key_out (either may be null; both null: only n_out) need room for `cap` >=
+ * that many.  Ordered classes follow one another; an entry of order_out is a read of the batch (a piece, where the batch is
+ * searched piece by piece), key_out = class index << 16 | database bin, the bin non-decreasing along a class. */
+int pgx_db_get_read_order(pgx_db *db, const pgx_reads *r, uint32_t *order_out, uint32_t *key_out, int64_t cap, int64_t *n_out);
 
 typedef struct {
 	int32_t read, subject;

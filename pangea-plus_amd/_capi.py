@@ -90,7 +90,7 @@ VOTE_DTYPE = np.dtype([("depth", "<i4"), ("name", "<u4", (7,)), ("votes", "u1", 
 SYMBOLS = [
     "pgx_last_error", "pgx_version", "pgx_init", "pgx_device_count", "pgx_current_device", "pgx_db_build", "pgx_db_open",
     "pgx_db_from_fasta", "pgx_db_close", "pgx_db_num_seqs", "pgx_db_num_bases", "pgx_db_seq_id",
-    "pgx_db_device_arrays", "pgx_db_get_shape", "pgx_db_alloc_like", "pgx_db_finish_import", "pgx_db_checksum", "pgx_blastn_run", "pgx_db_set_ungapped", "pgx_db_set_dust", "pgx_db_set_dust_each_search",
+    "pgx_db_device_arrays", "pgx_db_get_shape", "pgx_db_alloc_like", "pgx_db_finish_import", "pgx_db_checksum", "pgx_blastn_run", "pgx_db_set_ungapped", "pgx_db_set_dust", "pgx_db_set_dust_each_search", "pgx_db_set_read_order", "pgx_db_get_read_order",
     "pgx_soap_index", "pgx_soap_run", "pgx_soap_run_seeded", "pgx_tax_create", "pgx_tax_open", "pgx_tax_close", "pgx_tax_gi2taxid",
     "pgx_tax_node", "pgx_tax_names", "pgx_tax_format_node", "pgx_tax_format_name", "pgx_tax_cli", "pgx_free",
     "pgx_tax_lineage_batch", "pgx_taxcollect_file", "pgx_consensus_file", "pgx_synth_default", "pgx_db_from_synth",
@@ -119,6 +119,8 @@ def _declare(L):
     sig("pgx_db_subject_lineage", S, [V, I64])
     sig("pgx_db_set_ungapped", C.c_int, [V, C.c_int])
     sig("pgx_db_set_dust_each_search", C.c_int, [V, C.c_int])
+    sig("pgx_db_set_read_order", C.c_int, [V, C.c_int])
+    sig("pgx_db_get_read_order", C.c_int, [V, V, V, V, I64, V])
     sig("pgx_reads_count", I64, [V])
     sig("pgx_hits_count", I64, [V])
     sig("pgx_reads_from_synth", C.c_int, [V, I64, I64, V])
@@ -294,6 +296,20 @@ class Db(_Handle):
     def set_dust_each_search(self, flag):
         """S3d (query masking) recomputed inside every search through this handle, as BLAST runs it"""
         _check(lib().pgx_db_set_dust_each_search(self.ptr, 1 if flag else 0))
+
+    def set_read_order(self, mode):
+        """The seed stage walks its reads in database order: 0 automatic (the default), 1 always, 2 never."""
+        _check(lib().pgx_db_set_read_order(self.ptr, int(mode)))
+
+    def read_order(self, reads):
+        """(order, keys) of the last search through this handle, for tests: the reads (pieces) in the order the seed stage
+        walked them, and class index << 16 | database bin for each; empty when no class was ordered."""
+        n = C.c_int64()
+        _check(lib().pgx_db_get_read_order(self.ptr, reads.ptr, None, None, 0, C.byref(n)))
+        order, keys = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            _check(lib().pgx_db_get_read_order(self.ptr, reads.ptr, order.ctypes.data, keys.ctypes.data, n.value, C.byref(n)))
+        return order, keys
 
     def dust_bits(self, reads):
         """The handle's own DUST results for `reads` (the last search through it with set_dust_each_search(True)), as

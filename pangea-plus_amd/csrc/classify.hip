@@ -18,6 +18,10 @@
 //                 the ungapped extension, and for the gapped stage the anchor and the level estimate B0.  Hits are staged
 //                 in LDS per read and leave contiguously into the wave's chunk of the table (one atomic per chunk).
 //                 search_pipeline (below) measures it stage by stage in PGX_STAGE_PROBES builds.
+// k_read_order_keys
+//                 one lane per read of a large search class: the bin of the database its first probes point at.  The class is
+//                 sorted by it (rocPRIM, 16 key bits) and k_seed_extend walks that list, positions handed out in order, so that
+//                 the reads of a database region run together and the region's lines are fetched once (order_reads below).
 // k_scan_*, k_scatter_hits, k_merge_pieces
 //                 per-read offsets of the table; only fragmented reads are moved.
 // k_sort_consensus<32 / 64>
@@ -33,6 +37,9 @@
 #include "bitops.hpp"
 #include "consensus_core.hpp"
 #include "engine.hpp"
+#include "read_order.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
 
 namespace pgx {
 
@@ -336,6 +343,7 @@ constexpr int kStage = 128; // hits staged in LDS per wave between flushes
 constexpr int kDeal = 2;     // postings dealt per lane per round (independent loads in flight)
 constexpr int kQueue = 64 * (kDeal + 1); // candidate queue per wave (filled 64*kDeal at a time, drained at >= 64)
 constexpr int kWavesPerBlock = 4;
+constexpr int kOrderGrab = 4; // rounds of the seed kernel a wavefront takes from an ordered list's counter at a time
 
 // the ordered hit table is written once and read by a later call: streamed past the caches (the database words,
 // block records and subject records are what should stay in them)
@@ -707,6 +715,54 @@ __device__ __forceinline__ void process_candidate(const DbView &db, const uint64
 	}
 }
 
+// ------------------------------------------------------------------------------------------ reads in database order
+// The index as read_order_key (read_order.hpp) asks for it: non-temporal loads as in the seed kernel, nothing of it is used twice
+struct OrderIndexView {
+	const uint32_t *bucket_off, *postings;
+	int bits;
+	__device__ __forceinline__ OrderRange range(uint32_t kmer) const
+	{
+		const uint32_t b = seed_bucket(kmer, bits);
+		const uint32_t lo = __builtin_nontemporal_load(&bucket_off[b]);
+		return OrderRange{ lo, __builtin_nontemporal_load(&bucket_off[(uint64_t)b + 1]) - lo };
+	}
+	__device__ __forceinline__ uint32_t first(uint32_t lo) const { return __builtin_nontemporal_load(&postings[lo]); }
+};
+
+// One lane per read of a search class: its locus key (the bin of the database its first probes point at) and its number, the
+// pairs the sort takes.  `cls` goes into the key's upper half for pgx_db_get_read_order only: the sort looks at the bin bits.
+__global__ __launch_bounds__(256) void k_read_order_keys(DbView db, ReadsView rd, int shift, uint32_t last_bin, uint32_t cls,
+							 uint32_t *__restrict__ keys, uint32_t *__restrict__ vals)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= rd.n)
+		return;
+	const uint32_t r = rd.list ? rd.list[i] : i;
+	const int L = (int)rd.len[r];
+	uint32_t kmer[2][2] = { { 0, 0 }, { 0, 0 } };
+	bool usable[2][2] = { { false, false }, { false, false } };
+	if (L >= kOrderProbeLen) {
+		const uint32_t w0 = rd.woff[r];
+		const bool two = L >= kOrderProbe1 + kOrderProbeLen;
+#pragma unroll
+		for (int s = 0; s < 2; s++) {
+			const uint64_t *rw = (s ? rd.rc : rd.fwd) + w0;
+			const uint64_t *ra = s ? rd.rc_amb : rd.fwd_amb;
+			// (probes 0 and 13 lie in the strand's first word: 29 <= 32 bases)
+			const uint64_t a = ra ? ra[w0] : 0ull;
+			kmer[s][0] = window16(rw, kOrderProbe0);
+			usable[s][0] = (uint32_t)a == 0u;
+			if (two) {
+				kmer[s][1] = window16(rw, kOrderProbe1);
+				usable[s][1] = (uint32_t)(a >> (2 * kOrderProbe1)) == 0u;
+			}
+		}
+	}
+	const OrderIndexView ix = { db.bucket_off, db.postings, db.bits };
+	keys[i] = read_order_key(ix, kmer, usable, shift, last_bin) | (cls << 16);
+	vals[i] = r;
+}
+
 // All LDS traffic of these kernels is wave-private (each wave owns its slice), and a wave's LDS operations
 // execute in issue order.  The fence therefore only has to stop the compiler from moving memory operations
 // across it and to drain the wave's own LDS queue; it deliberately does NOT wait for outstanding global
@@ -751,7 +807,27 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, NW == 8 ? 3 : 4) void k_seed_e
 	unsigned int chunk_used = kChunk; // forces a reservation at the first flush
 	const unsigned long long lt_mask = lane ? (~0ull >> (64 - lane)) : 0ull;
 
-	for (uint32_t rbase = (blockIdx.x * kWavesPerBlock + wave) * RPW; rbase < rd.n; rbase += gridDim.x * kWavesPerBlock * RPW) {
+	// A list in database order (rd.ticket, order_reads below) is handed out IN ORDER from one counter, kOrderGrab wavefront
+	// rounds at a time: under the fixed stride the wavefronts drift apart by tens of strides over the hundreds of rounds of a
+	// launch (a round's time follows its reads' candidates), and the positions in flight stop being neighbours -- the
+	// database lines of a region then leave L2 between two of its reads.  With the counter the positions in flight are the
+	// last 4 096 x kOrderGrab rounds handed out, whatever the wavefronts' pace.
+	uint32_t t_next = 0, t_end = 0;
+	auto next_round = [&](uint32_t cur) -> uint32_t {
+		if (!LISTED || !rd.ticket)
+			return cur + gridDim.x * kWavesPerBlock * RPW;
+		if (t_next == t_end) {
+			uint32_t t = 0;
+			if (lane == 0)
+				t = atomicAdd(rd.ticket, (uint32_t)(kOrderGrab * RPW));
+			t_next = __builtin_amdgcn_readfirstlane(t);
+			t_end = t_next + kOrderGrab * RPW;
+		}
+		const uint32_t r = t_next;
+		t_next += RPW;
+		return r;
+	};
+	for (uint32_t rbase = LISTED && rd.ticket ? next_round(0) : (blockIdx.x * kWavesPerBlock + wave) * RPW; rbase < rd.n; rbase = next_round(rbase)) {
 		// wave-uniform description of the (up to) two reads
 		const bool hasB = RPW == 2 && rbase + 1 < rd.n;
 		const uint32_t rA = LISTED ? rd.list[rbase] : rbase, rB = LISTED ? (hasB ? rd.list[rbase + 1] : 0u) : rbase + 1;
@@ -1858,6 +1934,7 @@ static ReadsView reads_view(const pgx_reads *rd)
 	v.woff = rd->d_woff.data();
 	v.n = (uint32_t)rd->n;
 	v.list = nullptr;
+	v.ticket = nullptr;
 	v.dustwin_f = rd->has_dust ? rd->dustb.win_f.data() : nullptr;
 	v.dustwin_r = rd->has_dust ? rd->dustb.win_r.data() : nullptr;
 	v.dust_any = rd->has_dust ? rd->dustb.any.data() : nullptr;
@@ -1898,7 +1975,7 @@ static ConsView cons_view(const pgx_db *db, const pgx_rdp *rdp)
 
 // stage boundaries on the pipeline's stream; read only after the one synchronisation at the end of the step
 struct StageEvents {
-	static constexpr int kN = 8;
+	static constexpr int kN = 10;
 	hipEvent_t e[kN] = {};
 	bool ok = false;
 	int init()
@@ -1979,6 +2056,13 @@ struct Workspace {
 	DevBuf<pgx_consensus_rec> recs;
 	GappedWork gapped;
 	DustBufs dust; // S3d computed inside a search (pgx_db_set_dust_each_search) lands here, never in the caller's batch
+	// reads in database order (order_reads): per search class that was ordered, at the class's place among the ordered ones,
+	// (locus key, read) pairs as made and as sorted; order_list is what the seed kernel walks.  Never the batch's own lists:
+	// a search only reads its batch
+	DevBuf<uint32_t> order_key_in, order_val_in, order_key, order_list;
+	DevBuf<uint8_t> order_tmp;
+	DevBuf<uint32_t> order_ticket; // per class: the counter the seed kernel takes its list positions from
+	uint64_t order_n = 0; // entries of the last search's list (0: no class was ordered)
 	pgx_hits hits; // used when the caller does not keep the hit table
 	uint64_t hit_cap_hint = 0, ovf_cap_hint = 0;
 	double table_per_read_hint = 0.0; // the hit table belongs to the caller and is made per call: sized per read, not by the largest batch seen
@@ -2019,6 +2103,75 @@ int db_stream(pgx_db *db, hipStream_t *out)
 	return 0;
 }
 
+// ------------------------------------------------------------------------------------------ reads in database order
+// The seed kernel's requests to the database words and block records are addressed by database position, and reads of a
+// batch arrive in random order: every such request is an L2 miss although a hundred reads of the batch want the same line.
+// Walking the reads in the order of their locus key (read_order.hpp) puts those hundred reads next to one another in time.
+// It costs a key kernel (about three random lines per read) and a radix sort of (16-bit key, read) pairs per class.
+// Auto rule (pgx_db_set_read_order 0): a class is ordered when it has at least kOrderMinReads reads and the database words do
+// not fit the L2s anyway (kOrderMinDbBytes); below either, the launch is the unordered one with its fixed stride.
+// Measured against 1 Gbp: 9.3 M reads of a class, seed stage 31.9 -> 30.1 ms with keys and sort inside;
+// 1.9 M reads, 6.92 -> 7.03 ms -- a fifth of the reads per database line, and the same tail of the launch.  The
+// threshold sits between the two, nearer the size that lost.
+constexpr uint64_t kOrderMinReads = 1u << 22;
+constexpr uint64_t kOrderMinDbBytes = 32ull << 20; // the packed bases against 8 x 4 MiB of L2: a smaller database is L2 hits in any order
+static bool order_wanted(const pgx_db *db, uint64_t class_reads)
+{
+	if (db->read_order == 1)
+		return class_reads > 0;
+	if (db->read_order == 2)
+		return false;
+	return class_reads >= kOrderMinReads && (uint64_t)db->n_bases / 4 >= kOrderMinDbBytes;
+}
+
+// Sorts every class of `sr` that qualifies into ws.order_list, on the search's stream.  ordered[c] = the class's offset in
+// the list, or -1.  Depends on the batch and the index alone: a repeated attempt of the search reuses it.
+static int order_reads(const pgx_db *db, const DbView &dv, const ReadsView &rv, const pgx_reads *sr, Workspace &ws,
+		       std::vector<int64_t> &ordered)
+{
+	hipStream_t st = ws.stream;
+	const std::vector<pgx_reads::SearchClass> &classes = sr->classes;
+	ordered.assign(classes.size(), -1);
+	const int shift = read_order_shift(dv.n_bases), key_bits = read_order_key_bits(dv.n_bases);
+	const uint32_t last_bin = read_order_last_bin(dv.n_bases);
+	uint64_t total = 0;
+	size_t tmp_bytes = 0; // the most any class's sort asks for
+	for (size_t c = 0; c < classes.size(); c++)
+		if (order_wanted(db, classes[c].count)) {
+			ordered[c] = (int64_t)total;
+			total += classes[c].count;
+			size_t bytes = 0;
+			PGX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
+							  (size_t)classes[c].count, 0, key_bits, st));
+			tmp_bytes = std::max(tmp_bytes, bytes);
+		}
+	ws.order_n = total;
+	if (total == 0)
+		return 0;
+	PGX_TRY(ws.order_key_in.ensure(total));
+	PGX_TRY(ws.order_val_in.ensure(total));
+	PGX_TRY(ws.order_key.ensure(total));
+	PGX_TRY(ws.order_list.ensure(total));
+	PGX_TRY(ws.order_tmp.ensure(tmp_bytes ? tmp_bytes : 1));
+	PGX_TRY(ws.order_ticket.ensure(classes.size()));
+	for (size_t c = 0; c < classes.size(); c++) {
+		if (ordered[c] < 0)
+			continue;
+		const uint64_t o = (uint64_t)ordered[c], cn = classes[c].count;
+		ReadsView cvw = rv;
+		cvw.n = (uint32_t)cn;
+		cvw.list = classes[c].listed ? sr->d_class_list.data() + classes[c].off : nullptr;
+		hipLaunchKernelGGL(k_read_order_keys, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0, st, dv, cvw, shift, last_bin, (uint32_t)c,
+				   ws.order_key_in.data() + o, ws.order_val_in.data() + o);
+		PGX_HIP(hipGetLastError());
+		size_t bytes = ws.order_tmp.n;
+		PGX_HIP(rocprim::radix_sort_pairs(ws.order_tmp.data(), bytes, ws.order_key_in.data() + o, ws.order_key.data() + o,
+						  ws.order_val_in.data() + o, ws.order_list.data() + o, (size_t)cn, 0, key_bits, st));
+	}
+	trace_point("order_reads");
+	return 0;
+}
+
 // search + gapped stage + group + order (+ consensus when rdp != null). d_recs: device array of n_reads records.
 int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out, pgx_consensus_rec *d_recs)
 {
@@ -2041,6 +2194,7 @@ int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out
 	hipStream_t st = ws.stream;
 	pgx_stage_times &tm = ws.times;
 	memset(&tm, 0, sizeof tm);
+	ws.order_n = 0;
 	const uint64_t n = (uint64_t)rd->n;
 	out->n_reads = rd->n;
 	PGX_TRY(out->d_read_cnt.ensure(n + 1));
@@ -2102,6 +2256,12 @@ int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out
 		}
 	}
 	ws.ev.mark(7, st);
+	// the reads of every class that qualifies in database order (part of the seed stage's time, once, whatever the attempts)
+	std::vector<int64_t> ordered;
+	PGX_TRY(order_reads(db, dv, rv, sr, ws, ordered));
+	const bool order_now = ws.order_n > 0;
+	if (order_now)
+		ws.ev.mark(8, st);
 	for (int attempt = 0;; attempt++) {
 		if (attempt > 8)
 			return fail(PGX_E_LIMIT, "hit tables did not settle after %d attempts", attempt);
@@ -2135,15 +2295,22 @@ int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out
 		uint32_t *big_count = reinterpret_cast<uint32_t *>(ws.counters.data() + 8), *mid_count = reinterpret_cast<uint32_t *>(ws.counters.data() + 9);
 		trace_point("search_pipeline: tables ready");
 		lap("tables ready");
+		if (order_now)
+			PGX_HIP(hipMemsetAsync(ws.order_ticket.data(), 0, classes.size() * sizeof(uint32_t), st));
 		ws.ev.mark(0, st);
 		uint32_t *rc_ptr = split ? ws.piece_cnt.data() : out->d_read_cnt.data(), *rs_ptr = read_start.data();
-		for (const pgx_reads::SearchClass &c0 : classes) {
-			pgx_reads::SearchClass c = c0;
+		for (size_t ci = 0; ci < classes.size(); ci++) {
+			pgx_reads::SearchClass c = classes[ci];
 			c.amb = c.amb || db->has_amb;
 			ReadsView cvw = rv;
 			const uint64_t cn = c.count;
 			cvw.n = (uint32_t)cn;
 			cvw.list = c.listed ? sr->d_class_list.data() + c.off : nullptr;
+			if (ordered[ci] >= 0) { // the class in database order: the listed form of the kernel over the workspace's list
+				c.listed = true;
+				cvw.list = ws.order_list.data() + ordered[ci];
+				cvw.ticket = ws.order_ticket.data() + ci;
+			}
 			const int per_block = kWavesPerBlock * (c.words > 0 ? 2 : 1);
 			const dim3 g((unsigned)std::min<uint64_t>((cn + per_block - 1) / per_block, 256ull * 8)), b(64 * kWavesPerBlock);
 #define PGX_SEED_LAUNCH2(A, W, D)                                                                                                  \
@@ -2287,11 +2454,11 @@ int search_pipeline(pgx_db *db, pgx_reads *rd, const pgx_rdp *rdp, pgx_hits *out
 	// HSPs the first tier listed: list A, plus ITS OWN appends to list B (list B's total also holds what the tier behind list A
 	// passed on: an HSP that went A -> B was counted twice); batches with one list: list A is the count
 	tm.gapped_wide = (int64_t)(uint32_t)h_cnt[kNCounters] + (int64_t)(uint32_t)(h_cnt[kNCounters + 2] >> 32);
-	tm.seed_extend_ms = ws.ev.ms(0, 1);
+	tm.seed_extend_ms = ws.ev.ms(0, 1) + (order_now ? ws.ev.ms(7, 8) : 0.0f); // (keys and sorts: once, not per attempt)
 	tm.gapped_ms = ws.ev.ms(1, 2);
 	tm.group_ms = ws.ev.ms(2, 3);
 	tm.sort_ms = ws.ev.ms(3, 4);
-	tm.total_ms = ws.ev.ms(0, 4);
+	tm.total_ms = ws.ev.ms(0, 4) + (order_now ? ws.ev.ms(7, 8) : 0.0f);
 	tm.dust_ms = dust_now ? ws.ev.ms(6, 7) : 0.0f; // (events 6 and 7 bracket the DUST passes alone: a repeated attempt is not in it)
 	tm.total_ms += tm.dust_ms;
 	// (PGX_HIT_LIMIT lowers the limit: tests use it to exercise the callers' batch halving)
@@ -2416,6 +2583,40 @@ int pgx_db_set_dust_each_search(pgx_db *db, int on)
 	if (!db)
 		return fail(PGX_E_ARG, "pgx_db_set_dust_each_search: null argument");
 	db->dust_each_search = on != 0;
+	return 0;
+}
+
+int pgx_db_set_read_order(pgx_db *db, int mode)
+{
+	if (!db || mode < 0 || mode > 2)
+		return fail(PGX_E_ARG, "pgx_db_set_read_order: null handle, or a mode other than 0 (auto), 1 (always), 2 (never)");
+	std::lock_guard<std::mutex> lock(db->search_mu);
+	db->read_order = mode;
+	return 0;
+}
+
+// the workspace's list of the last search through `db`, for tests
+int pgx_db_get_read_order(pgx_db *db, const pgx_reads *r, uint32_t *order_out, uint32_t *key_out, int64_t cap, int64_t *n_out)
+{
+	if (!db || !r || !n_out)
+		return fail(PGX_E_ARG, "pgx_db_get_read_order: null argument");
+	std::lock_guard<std::mutex> lock(db->search_mu);
+	if (!db->work)
+		return fail(PGX_E_ARG, "pgx_db_get_read_order: no search has run through this handle");
+	const Workspace &ws = *static_cast<const Workspace *>(db->work.get());
+	const pgx_reads *sr = r->pieces && r->pieces->n > 0 ? r->pieces.get() : r;
+	if ((int64_t)ws.order_n > sr->n)
+		return fail(PGX_E_ARG, "pgx_db_get_read_order: the last search through this handle was given another batch");
+	*n_out = (int64_t)ws.order_n;
+	if (!order_out && !key_out)
+		return 0;
+	if (cap < (int64_t)ws.order_n)
+		return fail(PGX_E_ARG, "pgx_db_get_read_order: room for %lld entries, the list holds %lld", (long long)cap, (long long)ws.order_n);
+	PGX_HIP(hipStreamSynchronize(ws.stream));
+	if (order_out)
+		PGX_TRY(ws.order_list.download(order_out, (size_t)ws.order_n));
+	if (key_out)
+		PGX_TRY(ws.order_key.download(key_out, (size_t)ws.order_n));
 	return 0;
 }
 

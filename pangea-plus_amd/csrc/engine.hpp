@@ -41,6 +41,7 @@ struct pgx_db {
 	std::mutex search_mu;       // searches through one handle are serialised; different handles share nothing
 	bool dust = true;      // pgx_db_set_dust: `-dust no` switches the low-complexity mask of the reads off
 	bool dust_each_search = false; // pgx_db_set_dust_each_search: S3d recomputed inside every search (as BLAST runs it), not only at import
+	int read_order = 0;    // pgx_db_set_read_order: the seed stage walks its reads in database order -- 0 auto, 1 always, 2 never
 	bool ungapped = false; // pgx_db_set_ungapped: searches through this handle stop after the ungapped stage (spec v1)
 	pgx::DevBuf<uint32_t> d_bucket_off, d_postings;
 	// databases without ambiguity: 12-byte records {posting, database bases left of the 16-mer, bases right of it}, the
@@ -299,6 +300,7 @@ struct ReadsView {
 	const uint32_t *len, *woff;
 	uint32_t n;           // reads this launch works on
 	const uint32_t *list; // their ids (null: 0 .. n-1): a batch is searched class by class (flag words, ambiguity)
+	uint32_t *ticket;     // a list in database order: the counter its positions are handed out from (null: fixed stride)
 };
 
 
