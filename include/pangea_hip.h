@@ -392,6 +392,36 @@ typedef struct {
 int pgx_unclassified_batch(pgx_db *db, const pgx_reads *reads, const pgx_hits *hits, const pgx_unclas_opts *o, uint8_t *mask_out,
 			   int64_t cap, int64_t *n_selected, pgx_reads **out);
 
+/* ---- the step before Trim: one FASTA per sample barcode ----------------------------------------------------------
+ * Barcode/barcode.pl:18-160 `-s reads.fas -b barcodes.txt -d dir`: argv is the script's @ARGV (no program name), walked as
+ * the script walks it (:29-43).  Per record the first sequence line that holds a barcode decides: every barcode in file
+ * order as a prefix of the line, else every barcode in file order as a substring (:164-211); the barcode is cut off, a
+ * read with bases < 100 by the script's own count (:258-268) is thrown out; the script's accidents -- `place = 1` for a
+ * prefix on a later line, the constant 60, the last record counted with the line total of the record before it -- are
+ * kept (tests/barcode_rule.py restates them).  Byte-identical bar<name>.fas per barcode, nobar.fas, barcode_count.txt and
+ * info.txt in `dir`; `log_text` = its stdout.  Refused, with nothing printed and nothing written: no -d, a barcode line
+ * with no tab / empty name / empty or non-alphabetic letters, a name with '/' or NUL or used twice, text before the first
+ * header line (PGX_E_ARG); more than 2048 barcodes or 64 letters (PGX_E_LIMIT); a last record on which the script never
+ * ends (PGX_E_REFHANG).  A file that cannot be created in `dir` returns PGX_E_IO with the stdout printed so far. */
+int pgx_barcode_file(int argc, const char *const *argv, char **log_text);
+/* The same run with its output kept in HBM: every output FASTA is a slice of one device buffer.  The accessors give the
+ * number of barcodes, name / letters / read count of barcode i (file order), the header lines seen, the reads without a
+ * barcode and the reads thrown out.  pgx_barcodes_take_reads makes of barcode i's slice the batch pgx_reads_from_fasta
+ * makes of bar<name>.fas (i = -1: of nobar.fas) through the device FASTA splitter, with no file and no host copy of the
+ * letters between; it may be called any number of times; a barcode with no reads gives the empty batch.  Batches are
+ * closed with pgx_reads_close, the result with pgx_barcodes_free. */
+typedef struct pgx_barcodes pgx_barcodes;
+int pgx_barcode_reads(const char *reads_path, const char *barcodes_path, pgx_barcodes **out);
+int64_t pgx_barcodes_count(const pgx_barcodes *b);
+const char *pgx_barcodes_name(const pgx_barcodes *b, int64_t i);
+const char *pgx_barcodes_letters(const pgx_barcodes *b, int64_t i);
+int64_t pgx_barcodes_reads(const pgx_barcodes *b, int64_t i);
+int64_t pgx_barcodes_sequences(const pgx_barcodes *b);
+int64_t pgx_barcodes_no_barcode(const pgx_barcodes *b);
+int64_t pgx_barcodes_thrown_out(const pgx_barcodes *b);
+int pgx_barcodes_take_reads(const pgx_barcodes *b, int64_t i, pgx_reads **out);
+void pgx_barcodes_free(pgx_barcodes *b);
+
 /* Columns 11-12 (e-value, bit score) of a `blastn -outfmt 6` row (README.md:96) for a raw score, as the row formatter
  * prints them: lambda 1.28, K 0.46 (reward 1 / penalty -2), BLAST+ tabular number formats.  Host arithmetic only.
  * The reference's only record of its BLAST dependency's output, validation_dataset/Data-set_2_consensus.xlsx

@@ -9,6 +9,6 @@ from ._capi import (  # noqa: F401
     PangeaError, lib, lib_path, init, device_count, version,
     SynthCfg, Db, Reads, Hits, Rdp, TaxDb, StageTimes,
     blastn, soap, soap_index, makeblastdb, tax_class, taxcollector, consensus, megaclust2, megaclustable, megaclust_batch, trim2,
-    unclassified_selector, unclassified,
+    unclassified_selector, unclassified, barcode, barcode_reads, Barcodes,
     TRIM_ROUTE_NONE, TRIM_ROUTE_PACKED, TRIM_ROUTE_TEXT,
 )

@@ -98,7 +98,7 @@ SYMBOLS = [
     "pgx_reads_get", "pgx_reads_get_dust", "pgx_db_get_dust", "pgx_blast_search", "pgx_hits_close", "pgx_hits_count", "pgx_hits_copy",
     "pgx_hits_read_offsets", "pgx_hits_read_counts", "pgx_hits_slice", "pgx_hits_format", "pgx_db_bind_taxonomy", "pgx_db_subject_lineage",
     "pgx_rdp_from_file", "pgx_rdp_from_synth", "pgx_rdp_close", "pgx_consensus_batch", "pgx_classify_consensus", "pgx_classify_consensus_tri", "pgx_vote3_batch", "pgx_vote3_format",
-    "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_unclas_file", "pgx_unclassified_batch", "pgx_trim_file", "pgx_trim_reads", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
+    "pgx_consensus_format", "pgx_consensus_format_file", "pgx_last_stage_times", "pgx_megaclust_file", "pgx_megaclust_batch", "pgx_megaclustable", "pgx_unclas_file", "pgx_unclassified_batch", "pgx_barcode_file", "pgx_barcode_reads", "pgx_barcodes_count", "pgx_barcodes_name", "pgx_barcodes_letters", "pgx_barcodes_reads", "pgx_barcodes_sequences", "pgx_barcodes_no_barcode", "pgx_barcodes_thrown_out", "pgx_barcodes_take_reads", "pgx_barcodes_free", "pgx_trim_file", "pgx_trim_reads", "pgx_blast_score_columns", "pgx_blast_score_columns_v", "pgx_probe_gather", "pgx_probe_issue", "pgx_probe_issue_name",
 ]
 
 
@@ -149,6 +149,15 @@ def _declare(L):
     sig("pgx_megaclustable", C.c_int, [C.c_int, V, V])
     sig("pgx_unclas_file", C.c_int, [C.c_int, V, V])
     sig("pgx_unclassified_batch", C.c_int, [V, V, V, V, V, I64, V, V])
+    sig("pgx_barcode_file", C.c_int, [C.c_int, V, V])
+    sig("pgx_barcode_reads", C.c_int, [S, S, V])
+    for name in ("pgx_barcodes_count", "pgx_barcodes_sequences", "pgx_barcodes_no_barcode", "pgx_barcodes_thrown_out"):
+        sig(name, I64, [V])
+    sig("pgx_barcodes_name", S, [V, I64])
+    sig("pgx_barcodes_letters", S, [V, I64])
+    sig("pgx_barcodes_reads", I64, [V, I64])
+    sig("pgx_barcodes_take_reads", C.c_int, [V, I64, V])
+    sig("pgx_barcodes_free", None, [V])
     sig("pgx_trim_file", C.c_int, [V, V, V, V, V])
     sig("pgx_trim_reads", C.c_int, [V, V, V, V, V])
     sig("pgx_probe_gather", C.c_int, [C.c_uint64, C.c_int, V, V])
@@ -632,11 +641,7 @@ def megaclustable(argv):
 _cwd_lock = threading.Lock()
 
 
-def unclassified_selector(argv, cwd=None):
-    """`perl Unclas_Sel/unclassified_selector.pl -m TABLE -s READS.fas -o OUT [-t PCT] [-e LN_EVALUE] [-b BITS]`; `argv` is
-    the word list after the script name, `cwd` the directory its file names are relative to (the messages echo the names as
-    given, so they are not rewritten: the call changes the process's directory for its duration).  Returns the script's
-    stdout; an -o file that cannot be created raises PangeaError (status -2) with the stdout so far as its `stdout`."""
+def _argv_verb(fn, argv, cwd):
     words = [os.fsencode(str(w)) for w in argv]
     arr = (C.c_char_p * max(1, len(words)))(*words)
     log = C.c_void_p()
@@ -645,7 +650,7 @@ def unclassified_selector(argv, cwd=None):
         if cwd is not None:
             os.chdir(cwd)
         try:
-            rc = lib().pgx_unclas_file(len(words), arr, C.byref(log))
+            rc = fn(len(words), arr, C.byref(log))
         finally:
             if back is not None:
                 os.chdir(back)
@@ -655,6 +660,14 @@ def unclassified_selector(argv, cwd=None):
         err.stdout = text
         raise err
     return text
+
+
+def unclassified_selector(argv, cwd=None):
+    """`perl Unclas_Sel/unclassified_selector.pl -m TABLE -s READS.fas -o OUT [-t PCT] [-e LN_EVALUE] [-b BITS]`; `argv` is
+    the word list after the script name, `cwd` the directory its file names are relative to (the messages echo the names as
+    given, so they are not rewritten: the call changes the process's directory for its duration).  Returns the script's
+    stdout; an -o file that cannot be created raises PangeaError (status -2) with the stdout so far as its `stdout`."""
+    return _argv_verb(lib().pgx_unclas_file, argv, cwd)
 
 
 class _UnclasOpts(C.Structure):
@@ -673,6 +686,56 @@ def unclassified(db, reads, hits, t=None, e=None, b=None, want_reads=True):
                                         C.byref(p) if want_reads else None))
     assert int(mask.sum()) == n_sel.value
     return mask, (Reads(p) if want_reads else None)
+
+
+def barcode(argv, cwd=None):
+    """`perl Barcode/barcode.pl -s READS.fas -b BARCODES.txt -d DIR`; `argv` is the word list after the script name, `cwd`
+    the directory its file names are relative to (as in unclassified_selector).  Writes bar<name>.fas per barcode, nobar.fas,
+    barcode_count.txt and info.txt into DIR and returns the script's stdout.  A refused input (include/pangea_hip.h lists
+    them) raises PangeaError with status -1, -7 or -6 and leaves DIR untouched."""
+    return _argv_verb(lib().pgx_barcode_file, argv, cwd)
+
+
+class Barcodes(_Handle):
+    """The result of barcode_reads(): counts on the host, every barcode's FASTA in HBM."""
+    _close = "pgx_barcodes_free"
+
+    def __len__(self):
+        return lib().pgx_barcodes_count(self.ptr)
+
+    def name(self, i):
+        return lib().pgx_barcodes_name(self.ptr, i)
+
+    def letters(self, i):
+        return lib().pgx_barcodes_letters(self.ptr, i)
+
+    def count(self, i):
+        return lib().pgx_barcodes_reads(self.ptr, i)
+
+    @property
+    def sequences(self):
+        return lib().pgx_barcodes_sequences(self.ptr)
+
+    @property
+    def no_barcode(self):
+        return lib().pgx_barcodes_no_barcode(self.ptr)
+
+    @property
+    def thrown_out(self):
+        return lib().pgx_barcodes_thrown_out(self.ptr)
+
+    def take_reads(self, i):
+        """the batch Reads.from_fasta makes of bar<name(i)>.fas (i = -1: of nobar.fas), built from the slice in HBM"""
+        p = C.c_void_p()
+        _check(lib().pgx_barcodes_take_reads(self.ptr, i, C.byref(p)))
+        return Reads(p)
+
+
+def barcode_reads(reads_path, barcodes_path):
+    """barcode() with its output kept in HBM: a Barcodes handle."""
+    p = C.c_void_p()
+    _check(lib().pgx_barcode_reads(_b(reads_path), _b(barcodes_path), C.byref(p)))
+    return Barcodes(p)
 
 
 def blast_score_columns(score, qlen, db_len, db_nseq, gapped=True):
